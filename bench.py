@@ -26,6 +26,10 @@ Prints ONE JSON line on rank 0 (contract in the task description), with a ``roof
 dominant kernel (HIP-event timed inside this process), a ``cpu_baseline`` object (the oracle's restatement of the
 same loop timed on the host cores, rank 0, N=1 only) and ``metric_delta_vs_cpu`` (GPU metrics of the first pairs
 against the oracle's full-length run on the same inputs).
+
+``--dump-outputs DIR`` writes, outside the timed region, what the last timed step computed (see ``outputs()`` of each
+workload) to DIR/<name>.npy, so that two builds run with the same arguments, hence the same inputs, can be compared
+output for output.  ``ms_per_step`` is the wall time of one timed step.
 """
 import argparse
 import json
@@ -47,6 +51,7 @@ PEAK_BF16_MFMA_TFLOPS = 2500.0
 PLANE_PRODUCTS = 6
 C = 3
 SIZES = [0.01, 0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7, 0.8, 0.9, 1.0]          # configs[2] size sweep (README.md:23)
+DUMP_BYTES = 64 * 10**6                                                      # --dump-outputs: all files together
 CONFIGS = {
     1: dict(name="configs[1]", H=16, T=50, batch=256, guidance=1.0, sf=(1.0, 0.5), seeds=(None, None)),
     4: dict(name="configs[4]", H=32, T=1000, batch=128, guidance=7.0, sf=(1.0, 1.0), seeds=(None, 4242)),
@@ -64,7 +69,12 @@ def parse():
     ap.add_argument("--no-profile", action="store_true", help="skip the per-kernel HIP-event timing")
     ap.add_argument("--batch", type=int, default=None, help="samples per GPU (default: the config's batch)")
     ap.add_argument("--serial", action="store_true", help="run the teacher and student loops back to back on one stream")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (rank 0)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ------------------------------------------------------------------------------------------- rank launcher
@@ -253,6 +263,14 @@ class PairWorkload:
                             for sf, ps in zip(self.spec["sf"], self.parts)}
         return vals
 
+    def outputs(self, vals):
+        """What a caller of the pass receives: the scalar metrics of every pair ([B x world] each, after the all-gather)
+        and this rank's teacher / student trajectories [T+1, B, E]."""
+        import numpy as np
+        out = {f"metric_{k}": np.asarray(vals[k]) for k in dump_metrics()}
+        out["teacher_trajectory"], out["student_trajectory"] = self.traj
+        return out
+
     def check(self, vals):
         import numpy as np
         return {"mean_endpoint_distance": float(np.mean(vals["endpoint_distance"])),
@@ -266,6 +284,7 @@ class GridWorkload:
         import torch
         from distillation_trajectories_amd.config import Config
         from distillation_trajectories_amd.models import DiffusionUNet
+        from distillation_trajectories_amd import engine
         from distillation_trajectories_amd.synthetic import make_model, noise_table
         self.torch, self.device, self.B, self.spec, self.rank = torch, device, batch, spec, rank
         self.collective = False
@@ -282,6 +301,7 @@ class GridWorkload:
         self.concurrent = concurrent
         self.units_per_step = (len(spec["sizes"]) + 1) * len(spec["scales"]) * batch * T
         self.parts = [[None], [None]]
+        self.keys = engine.SCALAR_KEYS + ("trajectory_mse_pre",)
 
     def describe(self, world):
         s = self.spec
@@ -294,9 +314,13 @@ class GridWorkload:
     def step(self, world, counts):
         from distillation_trajectories_amd import grid
         local = grid.hip_cell_metrics(self.teacher, self.students, self.cfg, self.spec["scales"], self.first, self.B,
-                                      self.device, table=self.table, streams=None if self.concurrent else 1)
+                                      self.device, table=self.table, streams=None if self.concurrent else 1, keys=self.keys)
         full = grid.all_gather_rows(local, counts, dim=2, force=True) if (world > 1 or self.collective) else local
         return full.cpu().numpy()
+
+    def outputs(self, vals):
+        """The scalar metrics of every cell, each float64 [size factor, guidance scale, sample (every rank's)]."""
+        return {f"metric_{k}": vals[..., self.keys.index(k)] for k in dump_metrics()}
 
     def check(self, vals):
         from distillation_trajectories_amd import engine
@@ -511,6 +535,49 @@ def traffic_from_profiles(kernel_name, config=1):
     return None
 
 
+def dump_metrics():
+    """Keys of the scalar metrics --dump-outputs writes: trajectory_mse as its pre-transform, 1000 x mean step-MSE, because
+    the reference's log1p(1 - x) of it is NaN for x > 2, as for the benchmark's diverging random-init models, and a NaN
+    hides any difference between two builds."""
+    from distillation_trajectories_amd import engine
+    return [k if k != "trajectory_mse" else "trajectory_mse_pre" for k in engine.SCALAR_KEYS]
+
+
+def dump_outputs(arrays, out_dir, limit=DUMP_BYTES):
+    """Write ``arrays`` (name -> numpy array or device tensor) to ``out_dir/<name>.npy`` as float32 / float64, at most
+    ``limit`` bytes in all.  Smallest first, each array may take an equal share of what is left.  One that does not fit
+    keeps a fixed sample of its rows (leading axes flattened, the last axis whole; the same rows for the same name and
+    shape in every run) and ``<name>_rows.npy`` lists the flat row numbers kept.  Returns {name: written shape}."""
+    import zlib
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: kv[1].numel() * kv[1].element_size() if torch.is_tensor(kv[1]) else kv[1].nbytes)
+    left = limit - 2 * 1024 * len(items)                # room for the .npy headers
+    shapes = {}
+    for i, (name, a) in enumerate(items):
+        share = left // (len(items) - i)
+        item = 4 if a.dtype == (torch.float32 if torch.is_tensor(a) else np.float32) else 8
+        width = a.shape[-1] if a.ndim > 1 else 1
+        n = a.numel() // width if torch.is_tensor(a) else a.size // width
+        rows = None
+        if n * width * item > share:
+            keep = share // (width * item + 8)
+            rows = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(n, keep, replace=False))
+            a = a.reshape(n, width)
+            a = a[torch.from_numpy(rows).to(a.device)] if torch.is_tensor(a) else a[rows]
+        host = a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        host = host.astype(np.float32 if item == 4 else np.float64, copy=False)
+        np.save(os.path.join(out_dir, name + ".npy"), host)
+        left -= host.nbytes
+        if rows is not None:
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+            left -= rows.nbytes
+            shapes[name + "_rows"] = list(rows.shape)
+        shapes[name] = list(host.shape)
+    return shapes
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -596,6 +663,8 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device=device if backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    # before the profiled pass below runs the steps again over the same buffers
+    dumped = dump_outputs(wl.outputs(vals), args.dump_outputs) if args.dump_outputs and rank == 0 else None
     # ---- the same K steps again with every launch bracketed by HIP events on the launch stream
     # (per-kernel durations for the roofline line; the ~2 event records per launch cost wall time,
     # so this pass is kept out of `value` and its own wall time is reported beside it)
@@ -628,6 +697,8 @@ def main():
                             if solo_group else None),
         "metric_check": wl.check(vals),
     }
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     # launch plans in use (engine._Plans): "table:<sha1>" = the committed per-arch table, "heuristic", "tuned:<sha1>" only with DT_AUTOTUNE=1
     from distillation_trajectories_amd import engine as _engine
     if args.config == 2:

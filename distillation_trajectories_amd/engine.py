@@ -645,7 +645,7 @@ SCALAR_KEYS = ("endpoint_distance", "mse", "trajectory_mse", "point_by_point_sim
 
 def batch_scalar_metrics(sums, w1, pixels, elems):
     """Vectorised form of ``metrics_from_sums`` for B equal-length pairs: {key: float64 array [B]} for the 19
-    scalar metrics (the per-step lists stay on the caller's side as sums / w1).
+    scalar metrics and ``trajectory_mse_pre`` (the per-step lists stay on the caller's side as sums / w1).
 
     sums float64 [B,n,4], w1 float64 [B,n].  Follows the same dtype path (fp32 where torch returned fp32
     scalars, float64 python arithmetic elsewhere, sequential accumulation where the reference loops)."""
@@ -664,7 +664,9 @@ def batch_scalar_metrics(sums, w1, pixels, elems):
         acc = np.zeros(B)
         for i in range(n):
             acc = acc + step_mse[:, i]
-        out["trajectory_mse"] = np.log1p(1.0 - (acc / n) * 1000)
+        # 1000 x mean step-MSE, before the reference's log1p(1 - x), which is NaN for x > 2: finite, and the value to compare
+        out["trajectory_mse_pre"] = (acc / n) * 1000
+        out["trajectory_mse"] = np.log1p(1.0 - out["trajectory_mse_pre"])
         meanD = D.mean(axis=1)
         out["point_by_point_similarity"] = np.exp(-5.0 * meanD)
         lms = 1.0 - np.log1p(mse * 5000) / np.log1p(5000)

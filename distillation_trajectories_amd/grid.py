@@ -65,8 +65,10 @@ def _upload(host):
     return host.pin_memory().to(torch.device("cuda", torch.cuda.current_device()), non_blocking=True)
 
 
-def hip_cell_metrics(teacher, students, cfg, guidance_scales, first_sample, count, device, table=None, streams=None):
-    """float64 tensor [n_sf, n_gs, count, K] on ``device`` for samples first_sample .. +count-1 (seed 42+s).
+def hip_cell_metrics(teacher, students, cfg, guidance_scales, first_sample, count, device, table=None, streams=None,
+                     keys=engine.SCALAR_KEYS):
+    """float64 tensor [n_sf, n_gs, count, len(keys)] on ``device`` for samples first_sample .. +count-1 (seed 42+s); ``keys``
+    are keys of engine.batch_scalar_metrics.
 
     The teacher runs once per CFG plan on the current stream, alone (see the note at its launch).  The students are
     independent of each other, so they then share the chip on ``streams`` side streams (default DT_GRID_STREAMS or 3),
@@ -165,8 +167,8 @@ def hip_cell_metrics(teacher, students, cfg, guidance_scales, first_sample, coun
     n_sf, n_rows = host.shape[0], host.shape[1]
     flat = host.reshape(n_sf * n_rows, 5 * n)
     vals = engine.batch_scalar_metrics(flat[:, : 4 * n].reshape(-1, n, 4), flat[:, 4 * n:], H * H, E)
-    per_row = np.stack([vals[k] for k in engine.SCALAR_KEYS], axis=1).reshape(n_sf, n_rows, K)
-    out = np.empty((n_sf, len(scales), count, K))
+    per_row = np.stack([vals[k] for k in keys], axis=1).reshape(n_sf, n_rows, len(keys))
+    out = np.empty((n_sf, len(scales), count, len(keys)))
     base = 0
     for group, X, block_of in t_groups:
         for gs, blk in zip(group, block_of):

@@ -436,11 +436,17 @@ def test_two_ranks_shard_the_grid_like_one(tmp_path):
 
     def run(gpus, batch):
         res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "2", "--gpus", str(gpus), "--batch", str(batch),
-                              "--steps", "1", "--warmup", "0", "--no-profile", "--no-cpu-baseline"], env=env, capture_output=True,
-                             text=True, timeout=600)
+                              "--steps", "1", "--warmup", "0", "--no-profile", "--no-cpu-baseline",
+                              "--dump-outputs", str(tmp_path / f"dump{gpus}")], env=env, capture_output=True, text=True, timeout=600)
         assert res.returncode == 0, res.stderr[-2000:]
         return json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
     two, one = run(2, 3), run(1, 6)
+    # rank 0 dumps every rank's cells after the all-gather: all finite, the same set of arrays as one rank's
+    assert sorted(os.listdir(tmp_path / "dump2")) == sorted(os.listdir(tmp_path / "dump1")) and os.listdir(tmp_path / "dump1")
+    for f in os.listdir(tmp_path / "dump1"):
+        for d in ("dump1", "dump2"):
+            a = np.load(tmp_path / d / f)
+            assert a.shape == (11, 4, 6) and np.all(np.isfinite(a)), (d, f)
     assert two["n_gpus"] == 2 and [r["rank"] for r in two["ranks"]] == [0, 1] and one["n_gpus"] == 1
     assert two["metric_check"]["cells"] == one["metric_check"]["cells"] == 11 * 4 * 6
     a, b = two["metric_check"]["path_length_similarity_sf0.5_gs3"], one["metric_check"]["path_length_similarity_sf0.5_gs3"]
