@@ -11,6 +11,10 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "lib
 COND_NONE, COND_ZERO, COND_ONE = 0, 1, 2
 RULE_ENGINE, RULE_PSAMPLE, RULE_MANAGER = 0, 1, 2
 PREC_FP32, PREC_SPLIT_BF16, PREC_AUTO = 0, 1, 2
+# convolution launch kinds (csrc/dt_internal.h ConvKind) as dt_unet_conv_choice reports them (+8: the block's 1x1 skip is folded
+# into that conv2 launch) and dt_unet_set_conv_choice / the plan table take them
+KIND_FP32 = 0
+KIND_NAMES = {KIND_FP32: "fp32", 1: "split-bf16", 3: "split-bf16-strip", 4: "split-bf16-strip32", 5: "split-bf16-stripk"}
 BT_COUNT, GT_COUNT, N_BLOCKS = 16, 9, 8
 ABI_VERSION = 4
 

@@ -15,8 +15,6 @@
 // identically for A and B, so the sum over k is complete and the result layout is the standard one:
 // acc register r of lane l = D[row (r&3)+8*(r>>2)+4*(l>>5)][col l&31], i.e. a register is a 128-B run
 // of consecutive channels for two pixel rows -> coalesced NHWC stores.
-#include <cstdlib>
-
 #include "dt_conv_epilogue.h"
 
 namespace dt {
@@ -146,31 +144,20 @@ int launch_conv(const ConvParams &p, hipStream_t s) {
   if (!p.in || !p.w || !p.scale || !p.shift || !p.out) return DT_E_NULL;
   if (p.cin_p % 16 || p.cout_p % 16 || p.n_p % kNPad || p.M <= 0) return DT_E_SHAPE;
   if ((long long)p.M * p.cin_p >= (1ll << 31) || (long long)p.M * p.cout_p * (p.n_dup > 1 ? p.n_dup : 1) >= (1ll << 31)) return DT_E_SHAPE;
-  int bm = p.bm, bn = p.bn;
-  if (!bm || !bn) {
-    const ConvChoice c = heuristic_choice(p.M, p.n_p, 1);
-    bm = c.bm; bn = c.bn;
-  }
-  if ((bm != 64 && bm != 128 && !(bm == 256 && bn == 64 && p.prec >= 3)) || (bn != 64 && bn != 128) || p.n_p % bn || p.prec == 2 ||
-      p.prec < 0 || p.prec > 5)
-    return DT_E_ARG;
-  const bool tall_m = bm == 128, wide_n = bn == 128;
-  dim3 grid((p.M + bm - 1) / bm, p.n_p / bn, p.splits);
-  if (p.splits < 1 || (p.splits > 1 && !p.slab)) return DT_E_ARG;
-  if (p.ccw < (p.cin_p >> 4) || (p.in2 && p.ccw2 < (p.cin2_p >> 4))) return DT_E_ARG;   // weight chunks per tap of the pack in use
-  if (p.prec >= 3 ? !chunks_fit(p.cin_p >> 4, p.ccw, p.splits * strip_kc(p.prec, bm, bn)) : (((p.tap_hi - p.tap_lo) * (p.cin_p >> 4)) % p.splits != 0)) return DT_E_ARG;
+  if (const int st = conv_admissible(p)) return st;
+  const bool tall_m = p.bm == 128, wide_n = p.bn == 128;
+  dim3 grid((p.M + p.bm - 1) / p.bm, p.n_p / p.bn, p.splits);
   // algorithmic flops: what the reference's conv2d does on the unpadded shape (all ksize^2 taps)
-  if (p.in2 && (p.splits != 1 || !p.w2 || !p.bias2 || p.cin2_p % 16)) return DT_E_ARG;
   const double flops = 2.0 * p.M * (double)p.cout_real * ((double)p.cin_real * p.ksize * p.ksize + (p.in2 ? p.cin2_real : 0));
-  if (p.prec >= 3) {
-    ProfileScope prof(p.prec == 5 ? (tall_m ? KC_CONVS_K128x64 : (wide_n ? KC_CONVS_K64x128 : KC_CONVS_K64x64)) : bm == 256 ? KC_CONVS_256x64 : tall_m ? (wide_n ? KC_CONVS_128x128 : KC_CONVS_128x64) : (wide_n ? KC_CONVS_64x128 : KC_CONVS_64x64),
+  if (is_strip(p.kind)) {
+    ProfileScope prof(p.kind == KIND_STRIPK ? (tall_m ? KC_CONVS_K128x64 : (wide_n ? KC_CONVS_K64x128 : KC_CONVS_K64x64)) : p.bm == 256 ? KC_CONVS_256x64 : tall_m ? (wide_n ? KC_CONVS_128x128 : KC_CONVS_128x64) : (wide_n ? KC_CONVS_64x128 : KC_CONVS_64x64),
                       flops, 4.0 * p.M * ((double)p.cin_real + p.cout_real), s);
-    const int st = launch_conv_strip(p, bm, bn, p.prec, s);
+    const int st = launch_conv_strip(p, s);
     if (st) return st;
-  } else if (p.prec == 1) {
+  } else if (p.kind == KIND_BF16) {
     ProfileScope prof(tall_m ? (wide_n ? KC_CONVB_128x128 : KC_CONVB_128x64) : (wide_n ? KC_CONVB_64x128 : KC_CONVB_64x64),
                       flops, 4.0 * p.M * ((double)p.cin_real + p.cout_real), s);
-    const int st = launch_conv_bf16x6(p, bm, bn, s);
+    const int st = launch_conv_bf16x6(p, p.bm, p.bn, s);
     if (st) return st;
   } else {
     ProfileScope prof(tall_m ? (wide_n ? KC_CONV_128x128 : KC_CONV_128x64) : (wide_n ? KC_CONV_64x128 : KC_CONV_64x64),
@@ -185,20 +172,89 @@ int launch_conv(const ConvParams &p, hipStream_t s) {
   return DT_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Launch rules.  A new kind or tile is a change here (vocabulary, resolution, admissibility) plus its launcher.
+
+// chunks per step of a strip kind: KIND_STRIP 1, KIND_STRIP2 2, KIND_STRIPK (K split across the waves) 4 waves x 1 chunk on
+// the 64 x 64 tile, 2 waves x 1 chunk on the 128 x 64 and 64 x 128 tiles
+int strip_kc(int kind, int bm, int bn) { return kind == KIND_STRIPK ? (bm == 64 && bn == 64 ? 4 : 2) : (kind == KIND_STRIP2 ? 2 : 1); }
+
+size_t strip_lds_bytes(int W, int bm, int bn, int kind) {
+  const int kc = strip_kc(kind, bm, bn);
+  const int R = bm + 2 * strip_halo(W, bm);
+  // the strip's three planes per chunk; the double-buffered weight tile unless the waves take their fragments from global memory (K split)
+  const size_t loop = (size_t)kc * ((size_t)3 * (((R + 7) & ~7) + 8) * 16 + (kind == KIND_STRIPK ? 0 : (size_t)2 * 3 * bn * 16)) * sizeof(__bf16);
+  // the staged epilogue reuses the same LDS: WM * 32 rows per copy, one copy per K-split wave (128 rows in every K-split layout but 64 x 128)
+  const size_t stage = (size_t)(bm == 256 || (kind == KIND_STRIPK && bn == 64) ? 128 : 64) * (bn + 4) * sizeof(float);
+  return loop > stage ? loop : stage;
+}
+
+// 2 (3) strip items per thread cover BM + 2(W+1) <= 256 (384) rows; the smallest strip tile fits LDS on such rows
+bool strip_reaches(int W) { return W + 1 <= 64 && strip_lds_bytes(W, 64, 64, KIND_STRIP) <= strip_lds_limit(KIND_STRIP); }
+
+// whether kind exists and has a bm x bn tile: 64 / 128 x 64 / 128 in every kind; 256 x 64 (4 x 1 wave layout) in the strip
+// kinds; with the K split across the waves only the tiles below 128 x 128
+static bool kind_has_tile(int kind, int bm, int bn) {
+  if (kind < KIND_FP32 || kind > KIND_STRIPK || kind == 2) return false;
+  if ((bm != 64 && bm != 128 && !(bm == 256 && bn == 64 && is_strip(kind))) || (bn != 64 && bn != 128)) return false;
+  return !(kind == KIND_STRIPK && (bm > 128 || (bm == 128 && bn == 128)));
+}
+
+bool conv_choice_valid(const ConvChoice &c, int slot, int n_p) {
+  if (!kind_has_tile(c.kind, c.bm, c.bn) || n_p % c.bn) return false;
+  if (c.splits < 1 || c.splits > 9 || c.splits == 5 || c.splits == 6 || c.splits == 7) return false;
+  return !c.fuse || (slot == 2 && c.splits == 1);
+}
+
 // Default tile + tap-split choice when a layer shape has not been autotuned: the widest N tile the
 // padded channel count allows, 128 rows once that still gives two workgroups per CU, and tap groups
 // so that small spatial levels (M = batch*4*4, batch*2*2 rows) still put >= 1.5 workgroups on every CU.
-ConvChoice heuristic_choice(int M, int n_p, int taps) {
-  ConvChoice c;
+static ConvChoice heuristic_choice(int M, int n_p, int taps) {
+  ConvChoice c{};   // (the kind is the precision mode's: resolve_conv_choice)
   c.bn = n_p % 128 == 0 ? 128 : 64;
   const long long blocks128 = (long long)((M + 127) / 128) * (n_p / c.bn);
   c.bm = blocks128 >= 512 ? 128 : 64;
   const long long blocks = (long long)((M + c.bm - 1) / c.bm) * (n_p / c.bn);
   c.splits = 1;
-  c.prec = 0;
   if (taps == 9 && M <= kSplitMaxRows && blocks < 384) c.splits = blocks * 3 >= 384 ? 3 : 9;
   c.fuse = c.splits == 1;   // fold a block's 1x1 skip into conv2 whenever conv2 is not tap-split
   return c;
+}
+
+ConvChoice resolve_conv_choice(const ConvLayer &L, const ConvChoice *req, int precision) {
+  ConvChoice c = req ? *req : heuristic_choice(L.M, L.n_p, L.splittable ? L.taps : 1);
+  const int cc = L.cin_p >> 4;
+  if (!req) {   // untuned default per mode; the strip kernel wherever the full 3x3 walk runs (uniformly >= the plain one)
+    c.kind = precision == DT_PREC_FP32 ? KIND_FP32 : KIND_BF16;
+    if (c.kind == KIND_BF16 && L.taps == 9 && strip_reaches(L.W)) {
+      c.kind = KIND_STRIP;   // tap groups 3 / 9 become channel-chunk groups 4 / 8 where they divide
+      c.splits = c.splits == 9 ? (cc % 8 == 0 ? 8 : (cc % 4 == 0 ? 4 : 1)) : (c.splits == 3 ? (cc % 4 == 0 ? 4 : (cc % 2 == 0 ? 2 : 1)) : 1);
+    }
+  }
+  if (c.kind == 2) c.kind = KIND_BF16;
+  if (is_strip(c.kind) && (L.taps != 9 || !strip_reaches(L.W))) c.kind = KIND_BF16;   // full 3x3 walks of rows <= 63 px only
+  if (c.kind == KIND_STRIPK && (c.bm > 128 || (c.bm == 128 && c.bn == 128))) c.kind = KIND_STRIP2;
+  if (c.bm == 256 && !is_strip(c.kind)) c.bm = 128;
+  if (!L.splittable) c.splits = 1;
+  if (is_strip(c.kind) ? !chunks_fit(cc, pack_chunks(L.cin_p), c.splits * strip_kc(c.kind, c.bm, c.bn)) : (L.taps * cc) % c.splits != 0)
+    c.splits = 1;
+  c.fuse = L.foldable && c.fuse && c.splits == 1;
+  return c;
+}
+
+int conv_admissible(const ConvParams &p) {
+  const int cc = p.cin_p >> 4;
+  if (!kind_has_tile(p.kind, p.bm, p.bn) || p.n_p % p.bn) return DT_E_ARG;
+  if (p.splits < 1 || (p.splits > 1 && !p.slab)) return DT_E_ARG;
+  if (p.ccw < cc || (p.in2 && p.ccw2 < (p.cin2_p >> 4))) return DT_E_ARG;   // weight chunks per tap of the pack in use
+  if (p.in2 && (p.splits != 1 || !p.w2 || !p.bias2 || p.cin2_p % 16)) return DT_E_ARG;
+  if (!is_strip(p.kind)) return (p.tap_hi - p.tap_lo) * cc % p.splits ? DT_E_ARG : DT_OK;
+  const int kc = strip_kc(p.kind, p.bm, p.bn);
+  if (p.ksize != 3 || p.tap_lo != 0 || p.tap_hi != 9 || !chunks_fit(cc, p.ccw, p.splits * kc)) return DT_E_ARG;
+  if (kc == 4 && p.W + 1 > 32) return DT_E_SHAPE;                  // one strip item per thread: BM + 2(W+1) <= 128 rows
+  if (p.in2 && !chunks_fit(p.cin2_p >> 4, p.ccw2, kc)) return DT_E_ARG;
+  if (p.W + 1 > 64) return DT_E_SHAPE;
+  return strip_lds_bytes(p.W, p.bm, p.bn, p.kind) <= strip_lds_limit(p.kind) ? DT_OK : DT_E_SHAPE;
 }
 
 // sum of the split-K slabs in z order + the layer epilogue, float4 over channels.  S = compile-time slab count

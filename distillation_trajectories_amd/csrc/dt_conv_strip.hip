@@ -29,11 +29,6 @@ namespace dt {
 
 extern __shared__ __attribute__((aligned(16))) __bf16 strip_lds[];
 
-// Halo rows either side of the tile.  The corner taps reach W + 1 pixels back / ahead; when the tile starts at x = 0 and
-// ends at x = W - 1 (BM a multiple of W) those two reads are out-of-picture taps of the first / last row and go to the
-// zero rows anyway, so W rows are enough -- which is what lets the K = 32 tile fit twice per CU at W = 16.
-__host__ __device__ inline int strip_halo(int W, int bm) { return bm % W == 0 ? W : W + 1; }
-
 // ABL != 0: timing experiments (wrong results): 1 no per-tap barrier, 2 no weight staging, 3 no MFMA,
 // 4 no fragment reads after the first step, 5 no strip re-staging
 // KC = 16-channel chunks staged and multiplied per step (1 or 2): KC = 2 halves the barriers and doubles the
@@ -505,45 +500,19 @@ __global__ __launch_bounds__(256, KC == 1 ? 3 : 2) void conv_strip_bf16x6_kernel
   }
 }
 
-// chunks per step of a strip arithmetic code: 3 -> 1, 4 -> 2, 5 (K split across the waves) -> 4 waves x 1 chunk on the
-// 64 x 64 tile, 2 waves x 1 chunk on the 128 x 64 and 64 x 128 tiles
-int strip_kc(int prec, int bm, int bn) { return prec == 5 ? (bm == 64 && bn == 64 ? 4 : 2) : (prec == 4 ? 2 : 1); }
-
-static size_t strip_lds_bytes(int W, int bm, int bn, int prec) {
-  const int kc = strip_kc(prec, bm, bn);
-  const int R = bm + 2 * strip_halo(W, bm);
-  // the strip's three planes per chunk; the double-buffered weight tile unless the waves take their fragments from global memory (K split)
-  const size_t loop = (size_t)kc * ((size_t)3 * (((R + 7) & ~7) + 8) * 16 + (prec == 5 ? 0 : (size_t)2 * 3 * bn * 16)) * sizeof(__bf16);
-  // the staged epilogue reuses the same LDS: WM * 32 rows per copy, one copy per K-split wave (128 rows in every K-split layout but 64 x 128)
-  const size_t stage = (size_t)(bm == 256 || (prec == 5 && bn == 64) ? 128 : 64) * (bn + 4) * sizeof(float);
-  return loop > stage ? loop : stage;
-}
-
-bool strip_admissible(int W, int bm, int bn, int prec) {
-  if (W + 1 > 64) return false;                                    // 2 (3) strip items per thread cover BM + 2(W+1) <= 256 (384) rows
-  if (bm == 256 && (bn != 64 || prec == 5)) return false;          // the 4 x 1 wave layout exists for 64-column tiles only
-  if (prec == 5 && (bm > 128 || (bm == 128 && bn == 128))) return false;
-  if (strip_kc(prec, bm, bn) == 4 && W + 1 > 32) return false;     // one strip item per thread: BM + 2(W+1) <= 128 rows
-  return strip_lds_bytes(W, bm, bn, prec) <= (prec == 3 ? 65536u : 98304u);
-}
-
-int launch_conv_strip(const ConvParams &p_in, int bm, int bn, int prec, hipStream_t s) {
+// p passed conv_admissible (dt_conv.hip): a full 3x3 walk whose tile, chunk groups and LDS footprint the kind supports
+int launch_conv_strip(const ConvParams &p_in, hipStream_t s) {
   ConvParams p = p_in;
-  const int kc = strip_kc(prec, bm, bn);
-  if (p.ksize != 3 || p.tap_lo != 0 || p.tap_hi != 9 || p.splits < 1 || prec < 3 || prec > 5) return DT_E_ARG;
-  if (prec == 5 && (bm > 128 || (bm == 128 && bn == 128))) return DT_E_ARG;
-  if (kc == 4 && p.W + 1 > 32) return DT_E_SHAPE;
-  if (!chunks_fit(p.cin_p >> 4, p.ccw, p.splits * kc) || (p.in2 && !chunks_fit(p.cin2_p >> 4, p.ccw2, kc))) return DT_E_ARG;
-  if (p.W + 1 > 64) return DT_E_SHAPE;                             // 2 (3) strip items per thread cover BM + 2(W+1) <= 256 (384) rows
-  if (bm == 256 && bn != 64) return DT_E_ARG;
+  const int bm = p.bm, bn = p.bn, kind = p.kind;
+  const int kc = strip_kc(kind, bm, bn);
   dim3 grid((p.M + bm - 1) / bm, p.n_p / bn, p.splits);
-  size_t lds = strip_lds_bytes(p.W, bm, bn, prec);
+  size_t lds = strip_lds_bytes(p.W, bm, bn, kind);
   p.dup_stage2 = 0;
   if (p.n_dup == 2 && p.pool_out) {   // a second epilogue stage behind the first (and its K-split copies), if it fits this launch's LDS class
-    const size_t rows1 = bm == 256 || kc == 4 || (prec == 5 && bm == 128) ? 128 : 64;         // WK * WM * 32
-    const size_t rows2 = bm == 256 ? 128 : (bm == 128 ? 64 : 32);                              // WM * 32
-    const size_t need = (rows1 + (prec == 5 ? rows2 : rows1)) * (bn + 4) * sizeof(float);
-    if (need <= (prec == 3 ? 65536u : 98304u)) {
+    const size_t rows1 = bm == 256 || kc == 4 || (kind == KIND_STRIPK && bm == 128) ? 128 : 64;   // WK * WM * 32
+    const size_t rows2 = bm == 256 ? 128 : (bm == 128 ? 64 : 32);                                 // WM * 32
+    const size_t need = (rows1 + (kind == KIND_STRIPK ? rows2 : rows1)) * (bn + 4) * sizeof(float);
+    if (need <= strip_lds_limit(kind)) {
       p.dup_stage2 = 1;
       if (need > lds) lds = need;
     }
@@ -564,7 +533,7 @@ int launch_conv_strip(const ConvParams &p_in, int bm, int bn, int prec, hipStrea
     return DT_OK;
   }
 #endif
-  if (prec >= 4) {
+  if (kind != KIND_STRIP) {
     static std::once_flag attr_once;   // 128x128 needs 80 KB of dynamic LDS; launches come from several host threads
     static int attr_status = DT_OK;
     std::call_once(attr_once, [] {
@@ -582,10 +551,9 @@ int launch_conv_strip(const ConvParams &p_in, int bm, int bn, int prec, hipStrea
       }
     });
     if (attr_status != DT_OK) return attr_status;
-    if (lds > 98304) return DT_E_SHAPE;
-    if (prec == 5 && bn == 128) conv_strip_bf16x6_kernel<64, 128, 0, 2, 2><<<grid, 256, lds, s>>>(p);
-    else if (prec == 5 && bm == 64) conv_strip_bf16x6_kernel<64, 64, 0, 4, 4><<<grid, 256, lds, s>>>(p);
-    else if (prec == 5) conv_strip_bf16x6_kernel<128, 64, 0, 2, 2><<<grid, 256, lds, s>>>(p);
+    if (kind == KIND_STRIPK && bn == 128) conv_strip_bf16x6_kernel<64, 128, 0, 2, 2><<<grid, 256, lds, s>>>(p);
+    else if (kind == KIND_STRIPK && bm == 64) conv_strip_bf16x6_kernel<64, 64, 0, 4, 4><<<grid, 256, lds, s>>>(p);
+    else if (kind == KIND_STRIPK) conv_strip_bf16x6_kernel<128, 64, 0, 2, 2><<<grid, 256, lds, s>>>(p);
     else if (bm == 256) conv_strip_bf16x6_kernel<256, 64, 0, 2><<<grid, 256, lds, s>>>(p);
     else if (bm == 128 && bn == 128) conv_strip_bf16x6_kernel<128, 128, 0, 2><<<grid, 256, lds, s>>>(p);
     else if (bm == 128) conv_strip_bf16x6_kernel<128, 64, 0, 2><<<grid, 256, lds, s>>>(p);
@@ -594,7 +562,6 @@ int launch_conv_strip(const ConvParams &p_in, int bm, int bn, int prec, hipStrea
     DT_LAUNCH_CHECK();
     return DT_OK;
   }
-  if (lds > 65536) return DT_E_SHAPE;
   if (bm == 256) conv_strip_bf16x6_kernel<256, 64><<<grid, 256, lds, s>>>(p);
   else if (bm == 128 && bn == 128) conv_strip_bf16x6_kernel<128, 128><<<grid, 256, lds, s>>>(p);
   else if (bm == 128) conv_strip_bf16x6_kernel<128, 64><<<grid, 256, lds, s>>>(p);

@@ -62,6 +62,24 @@ constexpr int kChunkPad = 4;   // chunk granularity of the split-bf16 weight pac
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 // whether a walk of `cc` chunks in groups of `div` (K chunks per step x split-K slices) stays inside a pack of `ccw` chunks
 inline bool chunks_fit(int cc, int ccw, int div) { return div >= 1 && round_up(cc, div) <= ccw; }
+// 16-channel weight chunks per tap of a split-bf16 pack of cin_p input channels (zero chunks up to a multiple of kChunkPad)
+inline int pack_chunks(int cin_p) { return round_up(cin_p, 16 * kChunkPad) >> 4; }
+
+// Launch kinds of a convolution.  The numbers are part of the ABI (dt_unet_conv_choice / dt_unet_set_conv_choice, the plan
+// table plans/gfx950.json); 2 (round 1's LDS-DMA variant) is retired and rejected.
+enum ConvKind {
+  KIND_FP32 = 0,     // exact fp32 MFMA implicit GEMM (conv_gemm_kernel)
+  KIND_BF16 = 1,     // split-bf16 implicit GEMM (conv_gemm_bf16x6_kernel)
+  KIND_STRIP = 3,    // split-bf16 strip kernel (full 3x3 walks): one 16-channel chunk per step
+  KIND_STRIP2 = 4,   // strip kernel, two chunks (K = 32) per step
+  KIND_STRIPK = 5,   // strip kernel, the step's chunks split across the waves (tiles below 128 x 128)
+};
+inline bool is_strip(int kind) { return kind >= KIND_STRIP; }
+
+// Halo rows either side of a strip tile.  The corner taps reach W + 1 pixels back / ahead; when the tile starts at x = 0 and
+// ends at x = W - 1 (BM a multiple of W) those two reads are out-of-picture taps of the first / last row and go to the
+// zero rows anyway, so W rows are enough -- which is what lets the K = 32 tile fit twice per CU at W = 16.
+__host__ __device__ inline int strip_halo(int W, int bm) { return bm % W == 0 ? W : W + 1; }
 
 // One convolution expressed as an implicit GEMM over NHWC activations:
 //   out[m][n] = epilogue( sum_{tap,c} in[pixel(m)+tap][c] * w[tap][c][n] )
@@ -86,10 +104,8 @@ struct ConvParams {
   // accumulators to slab[z][M][cout_p]; splitk_epilogue then sums the slabs in z order (deterministic)
   int splits;
   float *slab;
-  int bm, bn;          // tile override (0 = pick by heuristic); bn = 128 needs n_p % 128 == 0
-  int prec;            // 0: exact fp32 MFMA (w = fp32 pack), 1: split-bf16 (w = bf16x3 pack), 2: unused,
-                       // 3: split-bf16 strip kernel (3x3 only; `splits` then divides the channel chunks, not the taps),
-                       // 4: strip kernel with two channel chunks (K = 32) per step
+  int bm, bn;          // tile; bn = 128 needs n_p % 128 == 0
+  int kind;            // ConvKind (w: fp32 pack for KIND_FP32, else bf16x3 pack); strip kinds split channel chunks, not taps
   // enc1's 1x1 skip of the C <= 3 channel image x[imgs][C][H*W] (NCHW, shared by all passes), recomputed in the
   // epilogue instead of being materialised: add = sum_c x3[((m / hw) % imgs) * C * hw + c * hw + m % hw] * w3[n*4+c] + w3[n*4+3]
   const float *x3;
@@ -138,16 +154,35 @@ struct ConvParams {
 
 int launch_conv(const ConvParams &p, hipStream_t s);
 int launch_conv_bf16x6(const ConvParams &p, int bm, int bn, hipStream_t s);
-int launch_conv_strip(const ConvParams &p, int bm, int bn, int prec, hipStream_t s);   // prec 3 / 4 / 5: 3x3 only
-int strip_kc(int prec, int bm, int bn);                         // 16-channel chunks per step of a strip arithmetic code
-// whether the strip kernel can run a bm x bn tile with kc chunks per step on rows of W pixels (staging reach, LDS)
-bool strip_admissible(int W, int bm, int bn, int prec);
+int launch_conv_strip(const ConvParams &p, hipStream_t s);    // the strip kinds; p passed conv_admissible
 // cin_w: padded input channels per tap of the pack (>= cin_p, multiple of 16 * kChunkPad; zeros beyond cin_p)
 int launch_pack_conv_bf16x3(const float *w_oihw, void *wp, int cout, int cin, int ksize, int cin_p, int cin_w, int n_p,
                             int split_c, int split_cp, hipStream_t s);
-struct ConvChoice { int bm, bn, splits, prec, fuse; };
-ConvChoice heuristic_choice(int M, int n_p, int taps);
 constexpr int kSplitMaxRows = 32768;   // split-K candidates only below this many GEMM rows (bounds the slab)
+
+// ---- launch rules of a convolution (dt_conv.hip): which choices exist, how a requested one resolves for a layer, and
+// whether a bound launch can run.  Every caller (the forward, the choice hooks, the autotuner, the launchers) goes through them.
+struct ConvChoice { int bm, bn, splits, kind, fuse; };
+// what the rules read of one convolution of a forward
+struct ConvLayer {
+  int M, W;           // GEMM rows, picture width
+  int n_p, cin_p;     // padded output / input channels
+  int taps;           // taps walked: 9 (full 3x3) or 1 (1x1 conv, or the centre tap of a 1x1 picture)
+  bool splittable;    // split-K has a slab: not enc1 (its conv2 keeps the fused image-skip epilogue), M <= kSplitMaxRows
+  bool foldable;      // conv2 of a block with a 1x1 skip conv (j > 0), which its K walk can take over
+};
+int strip_kc(int kind, int bm, int bn);      // 16-channel chunks per step of a strip kind
+size_t strip_lds_bytes(int W, int bm, int bn, int kind);   // dynamic LDS of a strip launch on rows of W pixels
+// dynamic LDS a strip launch may take: 64 KB for KIND_STRIP, 96 KB (two workgroups per CU) for the K = 32 kinds
+inline size_t strip_lds_limit(int kind) { return kind == KIND_STRIP ? 65536u : 98304u; }
+bool strip_reaches(int W);                   // whether some strip tile runs on rows of W pixels (staging reach, LDS)
+// vocabulary: what dt_unet_set_conv_choice accepts for a slot (0 skip, 1 conv1, 2 conv2) with n_p output channels
+bool conv_choice_valid(const ConvChoice &c, int slot, int n_p);
+// resolution: the choice a layer runs for a request (nullptr: the default of the precision mode DT_PREC_*); degrades what
+// the layer cannot run; fuse comes back 1 only where the skip is folded
+ConvChoice resolve_conv_choice(const ConvLayer &L, const ConvChoice *req, int precision);
+// admissibility of a bound launch: DT_OK, or the DT_E_ARG / DT_E_SHAPE that launch_conv returns for it
+int conv_admissible(const ConvParams &p);
 
 int launch_pack_conv(const float *w_oihw, float *wp, int cout, int cin, int ksize, int cin_p, int n_p,
                      int split_c, int split_cp, hipStream_t s);

@@ -11,6 +11,7 @@
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -214,8 +215,6 @@ const TunedShape *find_tuned(const dt_unet *u, int Bt, int H, int W, int imgs, i
   return nullptr;
 }
 
-// Parameters of conv slot `slot` (0 = 1x1 skip, 1 = conv1, 2 = conv2) of block j; returns false when the
-// block has no such launch (identity skips, and enc1 whose skip is recomputed in conv2's epilogue).
 void shape_images(const dt_unet *u, int Bt, int H, int W, int &imgs, int &single) {
   {
     std::lock_guard<std::mutex> lock(u->shape_mu);
@@ -233,127 +232,120 @@ void note_shape(const dt_unet *u, int Bt, int H, int W, int imgs, int single) {
   u->shapes.push_back(ShapeInfo{Bt, H, W, imgs, single});
 }
 
-// x_imgs images make up the Bt rows: every image once (pass 0), then the images from x_single on a second time (pass 1) when
-// Bt > x_imgs.  x_imgs <= 0 (tuning / reporting contexts): what the last forward of this row count used.
-bool conv_slot(const dt_unet *u, int j, int slot, const float *in, float *ws, const Plan &pl, int Bt, const float *tb,
-               int tb_div, const ConvChoice *choice, ConvParams &p, int x_imgs = 0, int x_single = 0) {
-  if (x_imgs <= 0) shape_images(u, Bt, pl.H[0], pl.W[0], x_imgs, x_single);
+// The launches of one forward shape, resolved once and free of pointers: the choice of every convolution slot (0 = 1x1 skip,
+// 1 = conv1, 2 = conv2) of every block and the per-block facts that follow from them.  bind_conv() binds one slot to buffers.
+// imgs images make up the Bt rows: every image once (pass 0), then the images from `single` on a second time (pass 1).
+struct ResolvedForward {
+  int Bt, H, W, imgs, single;
+  bool shared_enc1;                 // enc1 runs once over the images for all passes (its conv2 writes every pass)
+  ConvChoice c[kBlocks][3];         // c[j][2].fuse: conv2 folds the block's 1x1 skip in (slot 0 does not launch)
+  bool pool_fused[kBlocks];         // enc1..enc4: conv2's epilogue writes the 2x2 max pool
+  bool concat_in_place[kBlocks];    // dec3..dec1: conv1 and the folded skip read the concat's skip half from the encoder
+  bool head_fused;                  // dec1.conv2's epilogue evaluates the final 1x1 head
+};
+
+// whether slot `slot` of block j is a convolution of its own: enc1.conv1 is the direct first-layer kernel and enc1's skip is
+// recomputed in conv2's epilogue; identity skips have none
+bool has_launch(const dt_unet *u, int j, int slot) { return slot == 2 || (j > 0 && (slot == 1 || u->blk[j].has_res)); }
+
+ConvLayer conv_layer(const dt_unet *u, const ResolvedForward &f, int j, int slot) {
   const BlockW &k = u->blk[j];
+  const int h = f.H / kDiv[j], w = f.W / kDiv[j];
+  const int M = (j == 0 && f.shared_enc1 ? f.imgs : f.Bt) * h * w;
+  const int taps = slot == 0 || (h == 1 && w == 1) ? 1 : 9;   // a 1x1 image only ever sees the centre tap of a padded 3x3 kernel
+  return ConvLayer{M, w, k.n_p, slot == 2 ? k.cout_p : k.cin_p, taps, j > 0 && M <= kSplitMaxRows, slot == 2 && j > 0 && k.has_res};
+}
+
+ResolvedForward resolve_forward(const dt_unet *u, int Bt, int H, int W, int imgs, int single, const TunedShape *tuned) {
+  ResolvedForward f{};
+  f.Bt = Bt; f.H = H; f.W = W; f.imgs = imgs; f.single = single;
+  f.shared_enc1 = u->share_enc1 && (Bt + single) % imgs == 0;
+  for (int j = 0; j < kBlocks; ++j)
+    for (int slot = 0; slot < 3; ++slot)
+      if (has_launch(u, j, slot)) f.c[j][slot] = resolve_conv_choice(conv_layer(u, f, j, slot), tuned ? &tuned->c[j][slot] : nullptr, u->precision);
+  for (int j = 0; j < kBlocks; ++j) {
+    const ConvChoice &c2 = f.c[j][2];
+    const int h = H / kDiv[j], w = W / kDiv[j];
+    // encoder blocks enc1..enc4 feed a 2x2 max pool: folded into conv2's staged epilogue where a 32-row tile holds whole row
+    // pairs (W a power of two <= 16); split launches pool in their slab-summing epilogue kernel instead
+    f.pool_fused[j] = j <= 3 && h % 2 == 0 && w % 2 == 0 && (c2.splits > 1 || (w <= 16 && (w & (w - 1)) == 0));
+    // a decoder block reads the concat [upsampled | skip]: when both of its readers are strip launches (conv1, and the 1x1 skip
+    // folded into conv2) they fetch the skip half straight from the encoder's output and the concat holds the upsampled half only
+    f.concat_in_place[j] = j >= 5 && u->blk[j].has_res && is_strip(f.c[j][1].kind) && is_strip(c2.kind) && c2.fuse;
+  }
+  // dec1.conv2 also evaluates the final 1x1 head when its workgroups hold whole rows (one N tile, no split): the head is dec1's
+  // only consumer, so dec1's own output is then never written
+  const ConvChoice &last = f.c[kBlocks - 1][2];
+  f.head_fused = u->head_fusion && last.splits == 1 && u->blk[kBlocks - 1].n_p == last.bn && u->desc.channels <= 3;
+  return f;
+}
+
+// Parameters of slot `slot` of block j under choice c (the resolved one, or an autotuning candidate), bound to the workspace;
+// `in` is the block input (enc1: the NCHW image).  The pool / head epilogues follow f's choice of the slot.
+ConvParams bind_conv(const dt_unet *u, const ResolvedForward &f, int j, int slot, const ConvChoice &c, const float *in, float *ws,
+                     const Plan &pl, const float *tb, int tb_div) {
+  const BlockW &k = u->blk[j];
+  const ConvLayer L = conv_layer(u, f, j, slot);
   const int h = pl.H[j], w = pl.W[j];
-  const bool dot = h == 1 && w == 1;   // a 1x1 image only ever sees the centre tap of a padded 3x3 kernel
-  p = ConvParams{};
-  p.M = Bt * h * w; p.H = h; p.W = w;
-  p.cin_p = k.cin_p; p.cout_p = k.cout_p; p.n_p = k.n_p;
-  p.cin_real = k.cin; p.cout_real = k.cout;
+  ConvParams p{};
+  p.M = L.M; p.H = h; p.W = w;
+  p.cin_p = L.cin_p; p.cout_p = k.cout_p; p.n_p = k.n_p;
+  p.cin_real = slot == 2 ? k.cout : k.cin; p.cout_real = k.cout;
   p.tb_stride = u->tb_stride; p.m_per_tb = h * w * tb_div;
   p.slab = ws + pl.slab;
-  p.in = in;
-  int taps = 1;
+  p.in = slot == 2 ? ws + pl.h[j] : in;
+  p.ksize = slot == 0 ? 1 : 3;
+  p.tap_lo = slot > 0 && L.taps == 1 ? 4 : 0; p.tap_hi = p.tap_lo + L.taps;
+  p.relu = slot > 0;
   if (slot == 0) {
-    if (!k.has_res || j == 0) return false;
-    p.w = k.wr; p.scale = k.sr; p.shift = k.hr; p.out = ws + pl.r[j];
-    p.ksize = 1; p.tap_lo = 0; p.tap_hi = 1; p.relu = 0;
+    p.scale = k.sr; p.shift = k.hr; p.out = ws + pl.r[j];
   } else if (slot == 1) {
-    p.w = k.w1; p.scale = k.s1; p.shift = k.h1; p.tb = tb + k.tb_off; p.out = ws + pl.h[j]; p.relu = 1;
-    if (j == 0) {
-      return false;   // enc1.conv1 is the direct first-layer kernel (launch_first_conv), not an implicit GEMM
-    } else {
-      p.ksize = 3; p.tap_lo = dot ? 4 : 0; p.tap_hi = dot ? 5 : 9;
-      taps = dot ? 1 : 9;
-    }
+    p.scale = k.s1; p.shift = k.h1; p.tb = tb + k.tb_off; p.out = ws + pl.h[j];
   } else {
-    p.in = ws + pl.h[j]; p.cin_p = k.cout_p; p.cin_real = k.cout;
-    p.w = k.w2; p.scale = k.s2; p.shift = k.h2; p.out = ws + pl.o[j]; p.relu = 1;
-    p.ksize = 3; p.tap_lo = dot ? 4 : 0; p.tap_hi = dot ? 5 : 9;
-    taps = dot ? 1 : 9;
+    p.scale = k.s2; p.shift = k.h2; p.out = ws + pl.o[j];
+    if (f.pool_fused[j]) p.pool_out = ws + pl.pool[j];
     if (j == 0) {
       // the C-channel skip of enc1 is recomputed in the epilogue from the patches' centre taps (k = 9c+4)
-      p.x3 = in; p.w3 = k.w3; p.x3_hw = h * w; p.x3_imgs = x_imgs; p.x3_c = u->desc.channels;   // `in` is the NCHW image
-      taps = 1;   // keeps the fused (non-split) epilogue
-      if (u->share_enc1 && (Bt + x_single) % x_imgs == 0) {   // one launch over the x_imgs images for all their passes
-        p.M = x_imgs * h * w;
-        p.n_dup = (Bt + x_single) / x_imgs; p.dup_rows = p.M; p.dup_skip = x_single * h * w; p.tbc = tb + u->tb_cols;
-        p.skip_out = u->head_fusion ? 1 : 0;   // decided below once pool_out is known: only the pool reads enc1's output
+      p.x3 = in; p.w3 = k.w3; p.x3_hw = h * w; p.x3_imgs = f.imgs; p.x3_c = u->desc.channels;
+      if (f.shared_enc1) {   // one launch over the images for all their passes
+        p.n_dup = (f.Bt + f.single) / f.imgs; p.dup_rows = p.M; p.dup_skip = f.single * h * w; p.tbc = tb + u->tb_cols;
+        p.skip_out = u->head_fusion && p.pool_out ? 1 : 0;   // only the pool reads enc1's output (else a pooling launch does)
       }
     } else {
       p.add = k.has_res ? ws + pl.r[j] : in;   // identity skip: cin_p == cout_p
     }
-  }
-  ConvChoice c = choice ? *choice : heuristic_choice(p.M, p.n_p, taps);
-  if (!choice) {   // untuned default per mode; the strip kernel wherever the full 3x3 walk runs (uniformly >= the plain one)
-    c.prec = u->precision == DT_PREC_FP32 ? 0 : 1;
-    if (c.prec == 1 && p.ksize == 3 && p.tap_hi - p.tap_lo == 9 && strip_admissible(p.W, 64, 64, 3)) {
-      c.prec = 3;
-      const int cc = p.cin_p >> 4;   // tap groups 3 / 9 become channel-chunk groups 4 / 8 where they divide
-      c.splits = c.splits == 9 ? (cc % 8 == 0 ? 8 : (cc % 4 == 0 ? 4 : 1)) : (c.splits == 3 ? (cc % 4 == 0 ? 4 : (cc % 2 == 0 ? 2 : 1)) : 1);
+    if (j == kBlocks - 1 && f.head_fused) {
+      p.head_w = u->final_w; p.head_b = u->final_b; p.head_out = ws + pl.lowres;
+      p.head_c = u->desc.channels; p.head_cin = u->desc.dims[0];
     }
   }
-  if (c.prec == 2) c.prec = 1;
-  if (c.prec >= 3 && (p.tap_hi - p.tap_lo != 9 || !strip_admissible(p.W, 64, 64, 3))) c.prec = 1;   // full 3x3 walks of rows <= 63 px only
-  if (c.prec == 5 && (c.bm > 128 || (c.bm == 128 && c.bn == 128))) c.prec = 4;   // K split across waves: tiles below 128 x 128
-  // weight chunks per tap of the packs: the split-bf16 packs carry zero chunks up to a multiple of kChunkPad, so layers with an
-  // odd chunk count also run the kernels that multiply 2 / 4 chunks per step
-  const int cw_main = round_up(p.cin_p, 16 * kChunkPad) >> 4;
-  if (c.bm == 256 && c.prec < 3) c.bm = 128;                        // the 256-row tile exists in the strip kernels only
-  if (p.x3 || j == 0 || p.M > kSplitMaxRows) c.splits = 1;          // (enc1: no slab; its conv2 keeps the fused x3 epilogue)
-  if (c.prec >= 3 ? !chunks_fit(p.cin_p >> 4, cw_main, c.splits * strip_kc(c.prec, c.bm, c.bn))
-                  : (((p.tap_hi - p.tap_lo) * (p.cin_p >> 4)) % c.splits != 0)) c.splits = 1;
-  p.bm = c.bm; p.bn = c.bn; p.splits = c.splits; p.prec = c.prec;
-  p.ccw = c.prec >= 1 ? cw_main : p.cin_p >> 4;
-  // encoder blocks enc1..enc4 feed a 2x2 max pool: folded into this launch's staged epilogue where a 32-row tile holds
-  // whole row pairs (W a power of two <= 16); split launches pool in their slab-summing epilogue kernel instead
-  if (slot == 2 && j <= 3 && h % 2 == 0 && w % 2 == 0 && (c.splits > 1 || (w <= 16 && (w & (w - 1)) == 0))) p.pool_out = ws + pl.pool[j];
-  if (!p.pool_out) p.skip_out = 0;            // a separate pooling launch reads the full-resolution output
-  if (c.prec >= 1) p.w = slot == 0 ? k.wrb : (slot == 1 ? k.w1b : k.w2b);
-  // dec1.conv2 also evaluates the final 1x1 head when its workgroups hold whole rows (one N tile, no split): the head
-  // is dec1's only consumer, so dec1's own output is then never written
-  if (slot == 2 && j == kBlocks - 1 && u->head_fusion && c.splits == 1 && p.n_p == c.bn && u->desc.channels <= 3) {
-    p.head_w = u->final_w; p.head_b = u->final_b; p.head_out = ws + pl.lowres;
-    p.head_c = u->desc.channels; p.head_cin = u->desc.dims[0];
-  }
-  if (slot == 2 && c.fuse && c.splits == 1 && k.has_res && j > 0) {
-    // conv2 with the block's 1x1 skip folded into its K walk (the slot-0 launch is then skipped)
+  // the choice: tile, kind, the weight pack of the kind (and its chunk width), the folded skip walk where c folds it
+  const bool fp32 = c.kind == KIND_FP32;
+  p.bm = c.bm; p.bn = c.bn; p.splits = c.splits; p.kind = c.kind;
+  p.w = slot == 0 ? (fp32 ? k.wr : k.wrb) : (slot == 1 ? (fp32 ? k.w1 : k.w1b) : (fp32 ? k.w2 : k.w2b));
+  p.ccw = fp32 ? p.cin_p >> 4 : pack_chunks(p.cin_p);
+  if (c.fuse) {   // conv2 with the block's 1x1 skip folded into its K walk (the slot-0 launch is then skipped)
     p.add = nullptr;
-    p.in2 = in; p.w2 = c.prec >= 1 ? k.wrb : k.wr; p.bias2 = k.hr; p.cin2_p = k.cin_p; p.cin2_real = k.cin;
-    p.ccw2 = c.prec >= 1 ? k.cin_w >> 4 : k.cin_p >> 4;
+    p.in2 = in; p.w2 = fp32 ? k.wr : k.wrb; p.bias2 = k.hr; p.cin2_p = k.cin_p; p.cin2_real = k.cin;
+    p.ccw2 = fp32 ? k.cin_p >> 4 : k.cin_w >> 4;
   }
-  return true;
+  return p;
 }
 
-// Decoder block j reads the concat [upsampled | skip].  When both of its readers are strip launches (conv1, and the
-// 1x1 skip conv folded into conv2), they fetch the skip half straight from the encoder's output and the concat
-// buffer only ever holds the upsampled half.
-bool concat_in_place(const dt_unet *u, int j, float *ws, const Plan &pl, int Bt, const float *tb, int tb_div,
-                     const TunedShape *tuned) {
-  if (j < 5 || !u->blk[j].has_res) return false;
-  ConvParams c1, c2;
-  if (!conv_slot(u, j, 1, ws, ws, pl, Bt, tb, tb_div, tuned ? &tuned->c[j][1] : nullptr, c1)) return false;
-  if (!conv_slot(u, j, 2, ws, ws, pl, Bt, tb, tb_div, tuned ? &tuned->c[j][2] : nullptr, c2)) return false;
-  return c1.prec >= 3 && c1.prec <= 5 && c2.prec >= 3 && c2.prec <= 5 && c2.in2 != nullptr;
-}
-
-int run_block(const dt_unet *u, int j, const float *in, float *ws, const Plan &pl, int Bt, const float *tb, int tb_div,
-              const TunedShape *tuned, hipStream_t s, int x_imgs, int x_single) {
-  ConvParams p;
-  bool fused_skip = false;
-  if (u->blk[j].has_res && j > 0) {   // is conv2 going to fold the skip in?
-    ConvParams c2;
-    conv_slot(u, j, 2, in, ws, pl, Bt, tb, tb_div, tuned ? &tuned->c[j][2] : nullptr, c2);
-    fused_skip = c2.in2 != nullptr;
-  }
-  const bool in_place = concat_in_place(u, j, ws, pl, Bt, tb, tb_div, tuned);
+int run_block(const dt_unet *u, const ResolvedForward &f, int j, const float *in, float *ws, const Plan &pl, const float *tb,
+              int tb_div, hipStream_t s) {
   if (j == 0) {
     const BlockW &k = u->blk[0];
-    const bool shared = u->share_enc1 && (Bt + x_single) % x_imgs == 0;   // then the passes' time biases enter in conv2's epilogue
-    if (!shared && x_single) return DT_E_ARG;                // mixed batches exist in the shared-enc1 formulation only
-    const int st = launch_first_conv(in, k.w1, k.s1, k.h1, shared ? nullptr : tb + k.tb_off, u->tb_stride, tb_div, ws + pl.h[0], x_imgs,
-                                     shared ? 1 : Bt / x_imgs, u->desc.channels, pl.H[0], pl.W[0], k.cout, k.cout_p, s);
+    if (!f.shared_enc1 && f.single) return DT_E_ARG;   // mixed batches exist in the shared-enc1 formulation only
+    // (shared: the passes' time biases enter in conv2's epilogue)
+    const int st = launch_first_conv(in, k.w1, k.s1, k.h1, f.shared_enc1 ? nullptr : tb + k.tb_off, u->tb_stride, tb_div, ws + pl.h[0],
+                                     f.imgs, f.shared_enc1 ? 1 : f.Bt / f.imgs, u->desc.channels, pl.H[0], pl.W[0], k.cout, k.cout_p, s);
     if (st) return st;
   }
   for (int slot = 0; slot < 3; ++slot) {
-    if (slot == 0 && fused_skip) continue;
-    if (!conv_slot(u, j, slot, in, ws, pl, Bt, tb, tb_div, tuned ? &tuned->c[j][slot] : nullptr, p, x_imgs, x_single)) continue;
-    if (in_place) {
+    if (!has_launch(u, j, slot) || (slot == 0 && f.c[j][2].fuse)) continue;
+    ConvParams p = bind_conv(u, f, j, slot, f.c[j][slot], in, ws, pl, tb, tb_div);
+    if (f.concat_in_place[j]) {
       const int skip = 8 - j;            // dec3<-enc4(3), dec2<-enc3(2), dec1<-enc2(1)
       p.cc_a = u->blk[j].split_cp >> 4;
       p.b_stride = u->blk[skip].cout_p;
@@ -384,35 +376,29 @@ int forward_impl(const dt_unet *u, const float *x, int B, int n_pass, int H, int
     a.mode = FUSED_FORWARD; a.x = x; a.eps = eps;
     return launch_unet_fused(a, s);
   }
-  const TunedShape *tuned = find_tuned(u, Bt, H, W, B, B_single);
+  const ResolvedForward f = resolve_forward(u, Bt, H, W, B, B_single, find_tuned(u, Bt, H, W, B, B_single));
   int st = DT_OK;
   const float *cur = x;                     // enc1 reads the NCHW image itself (first-layer kernel, skip in conv2's epilogue)
   for (int j = 0; j < kBlocks; ++j) {
     if (j >= 1 && j <= 4) {        // encoder: pool the previous block's output (unless its conv2 already did)
-      ConvParams prev;
-      conv_slot(u, j - 1, 2, ws, ws, pl, Bt, tb, tb_div, tuned ? &tuned->c[j - 1][2] : nullptr, prev);
-      if (!prev.pool_out)
+      if (!f.pool_fused[j - 1])
       st = launch_maxpool(ws + pl.o[j - 1], ws + pl.pool[j - 1], Bt,
                           pl.H[j - 1], pl.W[j - 1], u->blk[j - 1].cout_p, s);
       if (st) return st;
       cur = ws + pl.pool[j - 1];
     } else if (j >= 5) {           // decoder: upsample previous output, concat the matching encoder output
       const int skip = 8 - j;      // dec3<-enc4(3), dec2<-enc3(2), dec1<-enc2(1)
-      const bool in_place = concat_in_place(u, j, ws, pl, Bt, tb, tb_div, tuned);
-      st = launch_upcat(ws + pl.o[j - 1], in_place ? nullptr : ws + pl.o[skip], ws + pl.cat[j - 5],
+      st = launch_upcat(ws + pl.o[j - 1], f.concat_in_place[j] ? nullptr : ws + pl.o[skip], ws + pl.cat[j - 5],
                         Bt, pl.H[j - 1], pl.W[j - 1], u->blk[j - 1].cout_p, u->blk[skip].cout_p, s);
       if (st) return st;
       cur = ws + pl.cat[j - 5];
     }
-    st = run_block(u, j, cur, ws, pl, Bt, tb, tb_div, tuned, s, B, B_single);
+    st = run_block(u, f, j, cur, ws, pl, tb, tb_div, s);
     if (st) return st;
   }
-  {   // head at the low resolution (unless dec1.conv2's epilogue already produced it), then the 3-channel upsample
-    ConvParams last;
-    conv_slot(u, kBlocks - 1, 2, ws, ws, pl, Bt, tb, tb_div, tuned ? &tuned->c[kBlocks - 1][2] : nullptr, last);
-    if (!last.head_out)
-      st = launch_head(ws + pl.o[7], u->final_w, u->final_b, ws + pl.lowres, Bt, pl.H[7], pl.W[7], u->blk[7].cout_p,
-                       u->desc.channels, u->desc.dims[0], s);
+  if (!f.head_fused) {   // head at the low resolution (unless dec1.conv2's epilogue already produced it), then the 3-channel upsample
+    st = launch_head(ws + pl.o[7], u->final_w, u->final_b, ws + pl.lowres, Bt, pl.H[7], pl.W[7], u->blk[7].cout_p,
+                     u->desc.channels, u->desc.dims[0], s);
     if (st) return st;
   }
   if (!eps) return DT_OK;                  // the sampler's fused update interpolates the low-resolution output itself
@@ -670,6 +656,10 @@ int dt_unet_forward(const dt_unet *h, const float *x, int B, int n_pass, int H, 
   return forward_impl(h, x, B, n_pass, H, W, tb, tb_div, eps, (float *)ws, ws_bytes, (hipStream_t)stream);
 }
 
+// launches are timed on an otherwise idle GPU, where extra workgroups are free, whereas in the sampler other streams fill idle
+// CUs: a split launch (slab traffic + one more launch) must be this much faster to be taken
+constexpr float kSplitMargin = 1.05f;
+
 // Times every admissible (tile, tap split) of every conv launch of one forward shape with HIP events on
 // `stream` (synchronises; call it outside hot loops and graph captures) and records the fastest.
 // Activations in the workspace are whatever the last forward left there (run one first: all-zero or
@@ -684,38 +674,29 @@ int dt_unet_autotune(dt_unet *h, int batch_total, int H, int W, void *workspace,
   hipEvent_t e0, e1;
   DT_HIP_TRY(hipEventCreate(&e0));
   DT_HIP_TRY(hipEventCreate(&e1));
-  TunedShape t{};
-  t.Bt = batch_total; t.H = H; t.W = W;
+  TunedShape t{batch_total, H, W, 0, 0, {}};
   shape_images(h, batch_total, H, W, t.imgs, t.single);   // the split of the last forward with this row count
+  const ResolvedForward f = resolve_forward(h, batch_total, H, W, t.imgs, t.single, nullptr);   // candidates start from the defaults
   const float *tb = h->slab;   // any readable floats: only timing matters here
   int st = DT_OK;
   {   // The clocks of an idle GPU take tens of milliseconds of load to settle (the same launch measures 15 % slower
       // cold): run one mid-sized layer for a while first so that the first candidates are not timed against a ramp.
-    ConvParams wp;
-    if (conv_slot(h, 1, 1, ws + pl.pool[0], ws, pl, batch_total, tb, batch_total, nullptr, wp))
-      for (int rep = 0; rep < 200 && st == DT_OK; ++rep) st = launch_conv(wp, s);
+    const ConvParams wp = bind_conv(h, f, 1, 1, f.c[1][1], ws + pl.pool[0], ws, pl, tb, batch_total);
+    for (int rep = 0; rep < 200 && st == DT_OK; ++rep) st = launch_conv(wp, s);
     if (hipStreamSynchronize(s) != hipSuccess) st = (int)hipGetLastError();
   }
   for (int j = 0; j < kBlocks && st == DT_OK; ++j) {
     const float *in = j == 0 ? ws + pl.h[0] : (j <= 4 ? ws + pl.pool[j - 1] : ws + pl.cat[j - 5]);   // (enc1: stands in for the image)
     float skip_ms = 0.f;
     for (int slot = 0; slot < 3 && st == DT_OK; ++slot) {
-      ConvParams p;
-      if (!conv_slot(h, j, slot, in, ws, pl, batch_total, tb, batch_total, nullptr, p)) continue;
-      {   // candidates start from the UNFUSED launch (the heuristic may have folded the skip in)
-        const ConvChoice unfused{p.bm, p.bn, p.splits, p.prec, 0};
-        conv_slot(h, j, slot, in, ws, pl, batch_total, tb, batch_total, &unfused, p);
-      }
-      const bool can_split = j > 0 && !p.x3 && p.M <= kSplitMaxRows;
-      const bool walk9 = p.tap_hi - p.tap_lo == 9;
-      ConvChoice best{p.bm, p.bn, p.splits, p.prec, 0};
+      if (!has_launch(h, j, slot)) continue;
+      ConvChoice best = f.c[j][slot];
+      best.fuse = 0;               // candidates start from the UNFUSED launch (the default may have folded the skip in)
+      const ConvLayer L = conv_layer(h, f, j, slot);
       float best_ms = 1e30f;
-      const bool can_fuse = slot == 2 && j > 0 && h->blk[j].has_res;
-      const BlockW &kw = h->blk[j];
-      const bool full3x3 = p.ksize == 3 && p.tap_hi - p.tap_lo == 9;
       // average milliseconds of `reps` back-to-back launches of one candidate (one warm launch first): in the sampler
       // launches queue behind each other, so a candidate is not charged the idle-queue launch latency per kernel
-      // (which would bias against split launches = two kernels); < 0: not admissible here
+      // (which would bias against split launches = two kernels); < 0: the launch cannot run here
       auto measure = [&](const ConvParams &q, int reps) -> float {
         int lst = launch_conv(q, s);
         if (lst == DT_E_SHAPE || lst == DT_E_ARG) return -1.f;
@@ -731,53 +712,34 @@ int dt_unet_autotune(dt_unet *h, int batch_total, int H, int W, void *workspace,
       };
       struct Cand { ConvChoice c; ConvParams q; float cost; };
       std::vector<Cand> cands;
-      static const float split_margin = getenv("DT_TUNE_SPLIT_MARGIN") ? (float)atof(getenv("DT_TUNE_SPLIT_MARGIN")) : 1.05f;
-      // a fused conv2 also saves the separate skip launch measured for slot 0; launches are timed on an otherwise idle
-      // GPU, where extra workgroups are free, whereas in the sampler other streams fill idle CUs: a split (slab traffic
-      // + one more launch) must win by a margin to be taken
+      // a fused conv2 also saves the separate skip launch measured for slot 0; a split must win by kSplitMargin
       auto cost_of = [&](float ms, const ConvChoice &c) {
-        return (ms + (c.fuse ? 0.f : (can_fuse ? skip_ms : 0.f))) * (c.splits > 1 ? split_margin : 1.0f);
+        return (ms + (c.fuse ? 0.f : (L.foldable ? skip_ms : 0.f))) * (c.splits > 1 ? kSplitMargin : 1.0f);
       };
-      // Kernel families worth timing (the search is paid once per model and shape, so it is pruned to what the
-      // per-layer tables show can win): exact-fp32 mode -> the fp32-MFMA kernel only; otherwise the strip kernels
-      // for full 3x3 walks and the plain split-bf16 kernel for everything else.
-      for (int prec = 0; prec <= 5 && st == DT_OK; ++prec) {
-        if (h->precision == DT_PREC_FP32 ? prec != 0 : prec == 0) continue;
-        if (prec == 2) continue;
-        static const int skip_mask = getenv("DT_TUNE_SKIP_PREC") ? atoi(getenv("DT_TUNE_SKIP_PREC")) : 0;   // experiments: bit p drops family p
-        if (skip_mask & (1 << prec)) continue;
-        const bool strip_ok = full3x3 && strip_admissible(p.W, 64, 64, 3);   // some strip tile fits this row width
-        if (prec >= 3 && !strip_ok) continue;
-        if (prec == 1 && strip_ok) continue;                                  // the plain kernel competes where the strip one cannot run
-      for (int bm = 64; bm <= 256; bm *= 2)
-        for (int bn = 64; bn <= 128; bn += 64) {
-          if (p.n_p % bn) continue;
-          if (bm == 256 && (prec < 3 || bn != 64)) continue;          // the 4 x 1 wave layout: strip kernels, 64-column tiles
-          if (prec == 5 && (bm > 128 || (bm == 128 && bn == 128))) continue;   // K split across the waves: tiles below 128 x 128
-          // dec1.conv2 with one N tile also evaluates the head (saves the head launch and dec1's output round trip)
-          if (j == kBlocks - 1 && slot == 2 && h->head_fusion && h->desc.channels <= 3 && p.n_p <= 128 && bn != p.n_p) continue;
-          // 3x3 walks split by taps 1/3/9; the strip kernel and single-tap layers by channel chunks 1/2/4/8
-          const long long tiles = (long long)((p.M + bm - 1) / bm) * (p.n_p / bn);
-          for (int sp = 1; sp <= (can_split ? 9 : 1); sp *= ((prec >= 3 || !walk9) ? 2 : 3))
-          for (int fuse = 0; fuse <= ((can_fuse && sp == 1) ? 1 : 0); ++fuse) {
-            if (prec >= 3 ? !chunks_fit(p.cin_p >> 4, round_up(p.cin_p, 16 * kChunkPad) >> 4, sp * strip_kc(prec, bm, bn))
-                          : (!walk9 && (p.cin_p >> 4) % sp)) continue;
-            if (prec >= 3 && !strip_admissible(p.W, bm, bn, prec)) continue;   // LDS footprint of this tile
-            if (sp > 1 && tiles * (sp / 2) >= 1024) continue;          // already >= 4 workgroups per CU without this split
-            ConvParams q = p;
-            q.bm = bm; q.bn = bn; q.splits = sp; q.prec = prec;
-            q.w = prec ? (slot == 0 ? kw.wrb : (slot == 1 ? kw.w1b : kw.w2b)) : (slot == 0 ? kw.wr : (slot == 1 ? kw.w1 : kw.w2));
-            q.ccw = prec ? round_up(p.cin_p, 16 * kChunkPad) >> 4 : p.cin_p >> 4;
-            if (fuse) {
-              q.add = nullptr; q.in2 = in; q.w2 = prec ? kw.wrb : kw.wr; q.bias2 = kw.hr; q.cin2_p = kw.cin_p;
-              q.cin2_real = kw.cin; q.ccw2 = prec ? kw.cin_w >> 4 : kw.cin_p >> 4;
-            }
-            const float ms = measure(q, 3);
-            if (ms < 0.f) continue;
-            const ConvChoice c{bm, bn, sp, prec, fuse};
-            cands.push_back(Cand{c, q, cost_of(ms, c)});
+      // Search policy (the search is paid once per model and shape, so it is pruned to what the per-layer tables show can
+      // win): exact-fp32 mode -> the fp32-MFMA kind only; otherwise the strip kinds for full 3x3 walks that some strip tile
+      // reaches and the plain split-bf16 kind for everything else.  Which candidates can run at all is conv_admissible's.
+      const bool strip_ok = L.taps == 9 && strip_reaches(L.W);
+      for (const int kind : {KIND_FP32, KIND_BF16, KIND_STRIP, KIND_STRIP2, KIND_STRIPK}) {
+        if (h->precision == DT_PREC_FP32 ? kind != KIND_FP32 : kind == KIND_FP32) continue;
+        if (is_strip(kind) ? !strip_ok : (kind == KIND_BF16 && strip_ok)) continue;
+        for (int bm = 64; bm <= 256; bm *= 2)
+          for (int bn = 64; bn <= 128; bn += 64) {
+            // dec1.conv2 with one N tile also evaluates the head (saves the head launch and dec1's output round trip)
+            if (j == kBlocks - 1 && slot == 2 && h->head_fusion && h->desc.channels <= 3 && L.n_p <= 128 && bn != L.n_p) continue;
+            // 3x3 walks split by taps 1/3/9; the strip kernel and single-tap layers by channel chunks 1/2/4/8
+            const long long tiles = (long long)((L.M + bm - 1) / bm) * (L.n_p / bn);
+            for (int sp = 1; sp <= (L.splittable ? 9 : 1); sp *= ((is_strip(kind) || L.taps != 9) ? 2 : 3))
+              for (int fuse = 0; fuse <= ((L.foldable && sp == 1) ? 1 : 0); ++fuse) {
+                if (sp > 1 && tiles * (sp / 2) >= 1024) continue;          // already >= 4 workgroups per CU without this split
+                const ConvChoice c{bm, bn, sp, kind, fuse};
+                const ConvParams q = bind_conv(h, f, j, slot, c, in, ws, pl, tb, batch_total);
+                if (conv_admissible(q) != DT_OK) continue;
+                const float ms = measure(q, 3);
+                if (ms < 0.f) continue;
+                cands.push_back(Cand{c, q, cost_of(ms, c)});
+              }
           }
-        }
       }
       // second look at the three cheapest: longer, interleaved runs (clock drift and timing noise otherwise flip
       // choices between near-equal candidates from run to run); ties within 1 % go to the later (larger-tile) candidate
@@ -805,9 +767,9 @@ int dt_unet_autotune(dt_unet *h, int batch_total, int H, int W, void *workspace,
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
   if (st != DT_OK) return st;
-  for (TunedShape &old : h->tuned)
-    if (old.Bt == t.Bt && old.H == t.H && old.W == t.W && old.imgs == t.imgs && old.single == t.single) { old = t; drop_graphs(h); return DT_OK; }
-  h->tuned.push_back(t);
+  TunedShape *old = const_cast<TunedShape *>(find_tuned(h, t.Bt, t.H, t.W, t.imgs, t.single));
+  if (old) *old = t;
+  else h->tuned.push_back(t);
   drop_graphs(h);
   return DT_OK;
 }
@@ -824,9 +786,12 @@ int dt_unet_time_conv(const dt_unet *h, int batch_total, int H, int W, int block
   if (pl.total * sizeof(float) > ws_bytes) return DT_E_WORKSPACE;
   float *ws = (float *)workspace;
   const float *in = block == 0 ? ws + pl.h[0] : (block <= 4 ? ws + pl.pool[block - 1] : ws + pl.cat[block - 5]);
-  const ConvChoice c{bm, bn, splits, prec, fuse};
-  ConvParams p;
-  if (!conv_slot(h, block, slot, in, ws, pl, batch_total, h->slab, batch_total, &c, p)) { *ms = 0.f; *flops = 0.0; return DT_OK; }
+  if (!has_launch(h, block, slot)) { *ms = 0.f; *flops = 0.0; return DT_OK; }
+  TunedShape req{};   // every slot asks for the choice: (block, slot) is bound with what follows from its own resolution only
+  std::fill_n(&req.c[0][0], kBlocks * 3, ConvChoice{bm, bn, splits, prec, fuse});
+  shape_images(h, batch_total, H, W, req.imgs, req.single);
+  const ResolvedForward f = resolve_forward(h, batch_total, H, W, req.imgs, req.single, &req);
+  ConvParams p = bind_conv(h, f, block, slot, f.c[block][slot], in, ws, pl, h->slab, batch_total);
   *flops = 2.0 * p.M * (double)p.cout_real * ((double)p.cin_real * p.ksize * p.ksize + (p.in2 ? p.cin2_real : 0));
 #ifdef DT_TOOLS
   if (const char *ab = getenv("DT_ABLATE")) p.ablate = atoi(ab);   // timing experiments only (tools build: build.py --tools)
@@ -880,23 +845,13 @@ int dt_unet_conv_choice(const dt_unet *h, int batch_total, int H, int W, int blo
                         int *splits, int *prec, int *tuned) {
   if (!h || !bm || !bn || !splits || !prec || !tuned) return DT_E_NULL;
   if (block < 0 || block >= kBlocks || slot < 0 || slot > 2 || H % 16 || W % 16 || batch_total < 1) return DT_E_ARG;
-  const Plan pl = make_plan(h, batch_total, H, W);
   int imgs = 0, single = 0;
   shape_images(h, batch_total, H, W, imgs, single);
   const TunedShape *t = find_tuned(h, batch_total, H, W, imgs, single);
-  ConvParams p;
-  float dummy = 0.f;
-  if (!conv_slot(h, block, slot, &dummy, &dummy, pl, batch_total, &dummy, 1, t ? &t->c[block][slot] : nullptr, p)) {
-    *bm = *bn = *splits = *prec = 0; *tuned = 0;
-    return DT_OK;
-  }
-  if (!p.bm || !p.bn) { const ConvChoice c = heuristic_choice(p.M, p.n_p, 1); p.bm = c.bm; p.bn = c.bn; }
-  *bm = p.bm; *bn = p.bn; *splits = p.splits; *prec = p.prec + (p.in2 ? 8 : 0); *tuned = t != nullptr;
-  if (slot == 0) {   // folded into conv2?
-    ConvParams c2;
-    conv_slot(h, block, 2, &dummy, &dummy, pl, batch_total, &dummy, 1, t ? &t->c[block][2] : nullptr, c2);
-    if (c2.in2) *bm = *bn = *splits = 0;
-  }
+  const ResolvedForward f = resolve_forward(h, batch_total, H, W, imgs, single, t);
+  const ConvChoice &c = f.c[block][slot];   // (all zero where the slot has no launch of its own)
+  *bm = c.bm; *bn = c.bn; *splits = c.splits; *prec = c.kind + (c.fuse ? 8 : 0); *tuned = t && has_launch(h, block, slot);
+  if (slot == 0 && f.c[block][2].fuse) *bm = *bn = *splits = 0;   // folded into conv2
   return DT_OK;
 }
 
@@ -913,33 +868,19 @@ int dt_unet_set_conv_choice(dt_unet *h, int batch_total, int H, int W, int block
   if (!h) return DT_E_NULL;
   if (block < 0 || block >= kBlocks || slot < 0 || slot > 2 || H < 16 || W < 16 || H % 16 || W % 16 || batch_total < 1)
     return DT_E_ARG;
-  if ((bm != 64 && bm != 128 && !(bm == 256 && bn == 64 && prec >= 3)) || (bn != 64 && bn != 128)) return DT_E_ARG;
-  if (splits < 1 || splits > 9 || prec < 0 || prec > 5 || (fuse && (slot != 2 || splits != 1))) return DT_E_ARG;
-  if (prec == 5 && (bm > 128 || (bm == 128 && bn == 128))) return DT_E_ARG;
-  if (splits == 5 || splits == 6 || splits == 7) return DT_E_ARG;
-  if (prec == 2) return DT_E_ARG;
-  if (h->blk[block].n_p % bn) return DT_E_ARG;
-  const Plan pl = make_plan(h, batch_total, H, W);
-  TunedShape *t = nullptr;
+  const ConvChoice c{bm, bn, splits, prec, fuse};
+  if (!conv_choice_valid(c, slot, h->blk[block].n_p)) return DT_E_ARG;
   int imgs = 0, single = 0;
   shape_images(h, batch_total, H, W, imgs, single);
-  for (TunedShape &old : h->tuned)
-    if (old.Bt == batch_total && old.H == H && old.W == W && old.imgs == imgs && old.single == single) t = &old;
+  TunedShape *t = const_cast<TunedShape *>(find_tuned(h, batch_total, H, W, imgs, single));
   if (!t) {   // start from what an untuned forward would launch
-    TunedShape fresh{};
-    fresh.Bt = batch_total; fresh.H = H; fresh.W = W; fresh.imgs = imgs; fresh.single = single;
-    float dummy = 0.f;
-    for (int j = 0; j < kBlocks; ++j)
-      for (int sl = 0; sl < 3; ++sl) {
-        ConvParams p;
-        if (!conv_slot(h, j, sl, &dummy, &dummy, pl, batch_total, &dummy, 1, nullptr, p)) continue;
-        if (!p.bm || !p.bn) { const ConvChoice c = heuristic_choice(p.M, p.n_p, 1); p.bm = c.bm; p.bn = c.bn; }
-        fresh.c[j][sl] = ConvChoice{p.bm, p.bn, p.splits, p.prec, p.in2 ? 1 : 0};
-      }
+    const ResolvedForward f = resolve_forward(h, batch_total, H, W, imgs, single, nullptr);
+    TunedShape fresh{batch_total, H, W, imgs, single, {}};
+    memcpy(fresh.c, f.c, sizeof(f.c));
     h->tuned.push_back(fresh);
     t = &h->tuned.back();
   }
-  t->c[block][slot] = ConvChoice{bm, bn, splits, prec, fuse};
+  t->c[block][slot] = c;
   drop_graphs(h);
   return DT_OK;
 }

@@ -256,7 +256,7 @@ class UNetHandle:
         arithmetic mode) is skipped, which leaves that slot on the heuristic."""
         ok = True
         for block, slot, bm, bn, sp, prec, fuse in plan:
-            if (self._mode == "fp32") != (prec == 0) and self._mode != "auto":
+            if (self._mode == "fp32") != (prec == _hip.KIND_FP32) and self._mode != "auto":
                 ok = False
                 continue
             if self.lib.dt_unet_set_conv_choice(self.h, rows, H, W, block, slot, bm, bn, sp, prec, fuse) != 0:
@@ -320,8 +320,7 @@ class UNetHandle:
                                                    ctypes.byref(sp), ctypes.byref(pr), ctypes.byref(tu)), "dt_unet_conv_choice")
                 if bm.value:
                     out.append((BLOCK_NAMES[j], ("skip", "conv1", "conv2")[slot], bm.value, bn.value, sp.value,
-                                ("fp32", "split-bf16", "-", "split-bf16-strip", "split-bf16-strip32", "split-bf16-stripk", "-", "-")[pr.value & 7]
-                                + ("+skip" if pr.value & 8 else ""), bool(tu.value)))
+                                _hip.KIND_NAMES.get(pr.value & 7, "-") + ("+skip" if pr.value & 8 else ""), bool(tu.value)))
         return out
 
     def time_bias(self, t_values, cond_modes):
