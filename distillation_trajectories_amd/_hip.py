@@ -16,7 +16,7 @@ PREC_FP32, PREC_SPLIT_BF16, PREC_AUTO = 0, 1, 2
 KIND_FP32 = 0
 KIND_NAMES = {KIND_FP32: "fp32", 1: "split-bf16", 3: "split-bf16-strip", 4: "split-bf16-strip32", 5: "split-bf16-stripk"}
 BT_COUNT, GT_COUNT, N_BLOCKS = 16, 9, 8
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 
 class HipLibraryError(RuntimeError):
@@ -77,6 +77,11 @@ SIGNATURES = {
                                 POINTER(c_double)]),
 }
 
+# name -> (restype, argtypes) of every symbol include/dt_hip_noise.h declares (the noise-prediction analysis, ABI 5)
+NOISE_SIGNATURES = {
+    "dt_q_sample": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+}
+
 
 def load(path=None):
     """Load (once) and return the library with argtypes set.  Raises HipLibraryError if absent."""
@@ -93,7 +98,7 @@ def load(path=None):
         lib = ctypes.CDLL(path)
     except OSError as e:
         raise HipLibraryError(f"cannot load {path}: {e}. There is no CPU fallback.") from e
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **NOISE_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -12,7 +12,8 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["dt_conv.hip", "dt_conv_bf16.hip", "dt_conv_strip.hip", "dt_layers.hip", "dt_update.hip", "dt_metrics.hip", "dt_fused.hip", "dt_unet.hip"]
-HEADERS = ["dt_internal.h", "dt_conv_epilogue.h", "dt_update_math.h", "dt_fused.h", os.path.join("..", "..", "include", "dt_hip.h")]
+HEADERS = ["dt_internal.h", "dt_conv_epilogue.h", "dt_update_math.h", "dt_fused.h", os.path.join("..", "..", "include", "dt_hip.h"),
+           os.path.join("..", "..", "include", "dt_hip_noise.h")]
 LIB = os.path.join(HERE, "libdt_hip.so")
 ARCH = "gfx950"
 
@@ -97,31 +98,41 @@ def build(force=False, verbose=False, tools=False):
 SAN_DRIVER = os.path.join(OBJ_DIR, "dt_host_sanitize")
 
 
-def build_sanitizer_driver(verbose=False):
-    """tests/host_sanitize/driver.cpp + every library source, HOST code instrumented with AddressSanitizer and
+NOISE_SAN_DRIVER = os.path.join(OBJ_DIR, "dt_host_sanitize_noise")
+
+
+def build_sanitizer_driver(verbose=False, driver="driver.cpp", out=SAN_DRIVER):
+    """tests/host_sanitize/<driver> + every library source, HOST code instrumented with AddressSanitizer and
     UndefinedBehaviorSanitizer (``-Xarch_host -fsanitize=...``; device code is left alone: GPU ASan is unavailable on this
-    pool), one executable csrc/_build/dt_host_sanitize.  Cross-compiles without a GPU; tests/test_host_sanitize.py runs it
-    on the GPU box."""
+    pool), one executable (default csrc/_build/dt_host_sanitize).  Cross-compiles without a GPU; tests/test_host_sanitize.py
+    runs it on the GPU box."""
     hipcc = hipcc_path()
     os.makedirs(OBJ_DIR, exist_ok=True)
     root = os.path.dirname(os.path.dirname(HERE))
-    driver = os.path.join(root, "tests", "host_sanitize", "driver.cpp")
+    driver = os.path.join(root, "tests", "host_sanitize", driver)
     deps = [os.path.join(HERE, f) for f in SOURCES + HEADERS] + [driver, os.path.abspath(__file__)]
-    if not _newer(SAN_DRIVER, deps):
-        return SAN_DRIVER
+    if not _newer(out, deps):
+        return out
     san = ["-Xarch_host", "-fsanitize=address", "-Xarch_host", "-fsanitize=undefined", "-Xarch_host", "-fno-omit-frame-pointer"]
     cmd = ([hipcc, f"--offload-arch={ARCH}", "-O1", "-g", "-std=c++17", "-Wno-unused-function", "-x", "hip"] + san +
-           [os.path.join(HERE, f) for f in SOURCES] + [driver, "-o", SAN_DRIVER])
+           [os.path.join(HERE, f) for f in SOURCES] + [driver, "-o", out])
     if verbose:
         print(" ".join(cmd), flush=True)
     res = subprocess.run(cmd, capture_output=True, text=True)
     if res.returncode != 0:
         sys.stderr.write(res.stdout + res.stderr)
         raise RuntimeError(f"sanitizer driver build failed with exit code {res.returncode}")
-    return SAN_DRIVER
+    return out
+
+
+def build_noise_sanitizer_driver(verbose=False):
+    """The same instrumented build around tests/host_sanitize/noise_driver.cpp, which walks every entry point of
+    include/dt_hip_noise.h: csrc/_build/dt_host_sanitize_noise (run by tests/test_hip_noise_analysis.py)."""
+    return build_sanitizer_driver(verbose, driver="noise_driver.cpp", out=NOISE_SAN_DRIVER)
 
 
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True, tools="--tools" in sys.argv))
     if "--sanitize" in sys.argv:
         print(build_sanitizer_driver(verbose=True))
+        print(build_noise_sanitizer_driver(verbose=True))

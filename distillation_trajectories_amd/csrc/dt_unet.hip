@@ -18,6 +18,7 @@
 
 #include "dt_fused.h"
 #include "dt_internal.h"
+#include "../../include/dt_hip_noise.h"
 
 namespace dt {
 int launch_cfg_update(int rule, const float *x, const float *eu, const float *ec, const float *z,
@@ -35,6 +36,7 @@ int launch_pair_metrics(const float *X, const float *Y, int n, int B, int E, dou
 int launch_pair_stats(const float *X, const float *Y, int n, int B, int E, double *out, hipStream_t s);
 int launch_sample_mean(const float *traj, int n, int B, int E, float *out, hipStream_t s);
 int launch_resize_bilinear(const float *in, float *out, int planes, int h, int w, int H, int W, hipStream_t s);
+int launch_q_sample(const float *x0, const float *z, const float *coef, int n_groups, int B, int E, float *out, hipStream_t s);
 }  // namespace dt
 
 using namespace dt;
@@ -1082,6 +1084,10 @@ int dt_traj_sample_mean(const float *traj, int n, int B, int E, float *out, void
 
 int dt_resize_bilinear(const float *in, float *out, int planes, int h, int w, int H, int W, void *stream) {
   return launch_resize_bilinear(in, out, planes, h, w, H, W, (hipStream_t)stream);
+}
+
+int dt_q_sample(const float *x0, const float *z, const float *coef, int n_groups, int B, int E, float *out, void *stream) {
+  return launch_q_sample(x0, z, coef, n_groups, B, E, out, (hipStream_t)stream);
 }
 
 int dt_traj_resampled_distance(const float *L, const float *S, int n_long, int n_short, int B, int E, double *out,

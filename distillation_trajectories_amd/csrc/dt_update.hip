@@ -5,6 +5,8 @@
 //   ENGINE : x' = c1*x - c2*eps ; x' += sigma*z       trajectory_engine.py:104-110
 //   PSAMPLE: x' = sra*(x - k*eps) + z*beta            utils/diffusion.py:149-158
 //   MANAGER: x' = (x - b*eps)/sqrt(a) ; x' += s*z     utils/trajectory_manager.py:196-203
+// and the forward noising of the noise-prediction analysis (q_sample_kernel below):
+//   x_t = sqrt(ab_t)*x0 + sqrt(1-ab_t)*z              analysis/noise_prediction/noise_analysis.py:268
 // x' is written straight into the next trajectory slot (which is the next step's input), so the
 // algorithmic HBM traffic is read x + read z + write x' = 3*E*4 B per sample-step, plus the eps
 // read(s).  All arithmetic is plain fp32 operators with fma contraction switched off, in the
@@ -137,6 +139,39 @@ int launch_cfg_update_lowres(int rule, const float *x, const float *lowres_u, co
     case DT_RULE_MANAGER: cfg_update_kernel<DT_RULE_MANAGER, true><<<blocks, 256, 0, s>>>(a); break;
     default: return DT_E_ARG;
   }
+  DT_LAUNCH_CHECK();
+  return DT_OK;
+}
+
+// Forward noising q(x_t | x_0) of n_groups timestep groups in one launch      analysis/noise_prediction/noise_analysis.py:268
+//   out[g][b][e] = a_g * x0[b][e] + s_g * z[g][b][e],   coef[g] = {a_g, s_g} = {sqrt(ab_t), sqrt(1 - ab_t)} (fp32, :253-262)
+// Two rounded products, then their rounded sum: the reference's torch expression, bit-identical to torch CPU for equal inputs.
+// x0 ([B][E], a few MB at most) is re-read by every group and stays in L2 / MALL; z and out stream once (float4 accesses).
+__global__ __launch_bounds__(256) void q_sample_kernel(const float4 *x0, const float4 *z, const float2 *coef, size_t be4,
+                                                       size_t total, float4 *out) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t g = i / be4;
+    const float2 c = coef[g];
+    const float4 xv = x0[i - g * be4], zv = z[i];
+    float4 o;
+    o.x = c.x * xv.x + c.y * zv.x;
+    o.y = c.x * xv.y + c.y * zv.y;
+    o.z = c.x * xv.z + c.y * zv.z;
+    o.w = c.x * xv.w + c.y * zv.w;
+    out[i] = o;
+  }
+}
+
+int launch_q_sample(const float *x0, const float *z, const float *coef, int n_groups, int B, int E, float *out, hipStream_t s) {
+  if (!x0 || !z || !coef || !out) return DT_E_NULL;
+  if (n_groups <= 0 || B <= 0 || E <= 0 || E % 4) return DT_E_SHAPE;
+  if (((uintptr_t)x0 | (uintptr_t)z | (uintptr_t)out) & 15 || (uintptr_t)coef & 7) return DT_E_ARG;   // float4 / float2 accesses
+  const size_t be4 = (size_t)B * (E / 4), total = (size_t)n_groups * be4;
+  const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+  // algorithmic bytes: read z + write out per group, x0 once
+  ProfileScope prof(KC_UPDATE, 3.0 * 4 * total, 4.0 * 4 * be4 * (2.0 * n_groups + 1.0), s);
+  q_sample_kernel<<<blocks, 256, 0, s>>>(reinterpret_cast<const float4 *>(x0), reinterpret_cast<const float4 *>(z),
+                                         reinterpret_cast<const float2 *>(coef), be4, total, reinterpret_cast<float4 *>(out));
   DT_LAUNCH_CHECK();
   return DT_OK;
 }

@@ -527,6 +527,22 @@ def device_pair_stats(X, Y):
     return out
 
 
+def q_sample(x0, z, coef):
+    """fp32 [G, B, ...] = coef[g, 0] * x0 + coef[g, 1] * z[g] for x0 [B, ...], z [G, B, ...] and coef [G, 2] (dt_q_sample:
+    the forward noising of the noise-prediction analysis, bit-identical to the torch expression)."""
+    lib = _hip.load()
+    _require_cuda(x0, "x0"); _require_cuda(z, "z"); _require_cuda(coef, "coef")
+    x0, z, coef = x0.contiguous().float(), z.contiguous().float(), coef.contiguous().float()
+    G, B = z.shape[0], x0.shape[0]
+    E = x0[0].numel()
+    if tuple(z.shape[1:]) != tuple(x0.shape) or tuple(coef.shape) != (G, 2):
+        raise HipLibraryError(f"q_sample: z {tuple(z.shape)} / coef {tuple(coef.shape)} do not match x0 {tuple(x0.shape)}")
+    out = torch.empty_like(z)
+    with torch.cuda.device(x0.device):
+        check(lib.dt_q_sample(ptr(x0), ptr(z), ptr(coef), G, B, E, ptr(out), stream_ptr()), "dt_q_sample")
+    return out
+
+
 def device_sample_mean(traj):
     """fp32 [n, E]: mean over the B samples of traj [n, B, E] (dt_traj_sample_mean)."""
     lib = _hip.load()

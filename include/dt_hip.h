@@ -32,8 +32,9 @@ extern "C" {
  *    dt_resize_bilinear;
  *    dt_sample_trajectory accepts eps_scratch_dev == NULL
  * 4: + dt_unet_set_fused / dt_unet_fused_active (small models: one launch per forward / per sampler call),
- *    dt_traj_pair_metrics (metric sums + Wasserstein term in one pass) */
-#define DT_ABI_VERSION 4
+ *    dt_traj_pair_metrics (metric sums + Wasserstein term in one pass)
+ * 5: + the forward-noising entry of the noise-prediction analysis, declared in include/dt_hip_noise.h */
+#define DT_ABI_VERSION 5
 
 enum {
   DT_OK = 0,
