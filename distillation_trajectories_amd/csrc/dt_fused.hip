@@ -427,8 +427,9 @@ __global__ __launch_bounds__(kThreads, 4) void unet_fused_kernel(const FusedArgs
     float v = 0.f;
     if (k < n_img && e < E) {
       if (a.mode == FUSED_FORWARD) {
+        // rows [pass 0 of all images | passes 1 .. n_pass-1 of images B_single ..]: r >= B walks those images once per pass
         const int r = row0 + k;
-        v = a.x[(size_t)(r < a.B ? r : r - a.B + a.B_single) * E + e];
+        v = a.x[(size_t)(r < a.B ? r : a.B_single + (r - a.B) % (a.B - a.B_single)) * E + e];
       } else {
         v = a.traj[(size_t)(img0 + k) * E + e];
       }

@@ -157,6 +157,7 @@ class UNetHandle:
         self._ws = {}
         self._consts = {}
         self._plans = {}              # (rows, H, W, images, single-pass images) -> plan id ("table:<sha1>", "tuned:<sha1>", "heuristic", "pinned")
+        self._pinned = set()          # (rows, H, W) of the shapes with launches pinned by hand (set_conv_choice)
         if not _FUSED_DEFAULT:
             self.set_fused(False)
 
@@ -214,6 +215,7 @@ class UNetHandle:
         check(self.lib.dt_unet_set_precision(self.h, int(mode)), "dt_unet_set_precision")
         self._mode = {0: "fp32", 1: "split-bf16", 2: "auto"}[int(mode)]
         self._plans.clear()               # the library drops its tuned shapes too: choices are per arithmetic mode
+        self._pinned = set()              # ... pins included: the next forward settles its plan afresh
 
     def set_fused(self, on):
         """Small models at 16x16: whole forward / whole sampler loop as one launch (dt_unet_set_fused); no-op for models
@@ -300,15 +302,21 @@ class UNetHandle:
         """{"rowsxHxW imgs/single": plan id} of every shape this handle has run (bench.py prints it)."""
         return {f"{k[0]}x{k[1]}x{k[2]} {k[3]}/{k[4]}": v for k, v in sorted(self._plans.items())}
 
-    def set_conv_choice(self, batch_total, H, W, block, slot, bm, bn, splits=1, prec=1, fuse=0):
+    def set_conv_choice(self, batch_total, H, W, block, slot, bm, bn, splits=1, prec=1, fuse=0, images=None, single=0):
         """Pin one convolution's launch choice for this forward shape (dt_unet_set_conv_choice).  A launch pinned by hand asks
-        for the layered kernels, so the handle leaves the fused small-model path (``set_fused(True)`` returns to it)."""
+        for the layered kernels, so the handle leaves the fused small-model path (``set_fused(True)`` returns to it).
+
+        The library keys a pin by the shape's split into images, and for a row count that has not run yet it assumes the
+        two-pass split (images = batch_total / 2): ``images`` (with ``single``, the single-pass images of a mixed batch)
+        declares the split of the forward the pin is meant for, e.g. ``images=batch_total`` for a one-pass forward."""
+        if images is not None:
+            check(self.lib.dt_unet_declare_shape(self.h, batch_total, H, W, images, single), "dt_unet_declare_shape")
         check(self.lib.dt_unet_set_conv_choice(self.h, batch_total, H, W, block, slot, bm, bn, splits, prec, fuse),
               "dt_unet_set_conv_choice")
         self.set_fused(False)
         for k in [k for k in self._plans if k[:3] == (batch_total, H, W)]:
             self._plans[k] = "pinned"
-        self._pinned = getattr(self, "_pinned", set()) | {(batch_total, H, W)}
+        self._pinned.add((batch_total, H, W))
 
     def conv_choices(self, batch_total, H, W):
         """[(block, slot, bm, bn, splits, tuned)] for reporting."""
@@ -367,7 +375,7 @@ class UNetHandle:
         return eps
 
     def _settle(self, rows, H, W, imgs, single, tune, warm):
-        if (rows, H, W) in getattr(self, "_pinned", ()):      # launches pinned by hand (tests, tools): leave them alone
+        if (rows, H, W) in self._pinned:      # launches pinned by hand (tests, tools): leave them alone
             self._plans.setdefault((rows, H, W, imgs, single), "pinned")
             return
         self.ensure_plan(rows, H, W, imgs, single, tune, warm)

@@ -1,0 +1,424 @@
+"""Every convolution launch choice, one U-Net block at a time, against a float64 evaluation of that block.
+
+For block j the test pins one of its convolutions (slot 0 skip, 1 conv1, 2 conv2) through dt_unet_set_conv_choice, runs the
+forward and reads block j's output (dt_unet_debug_activation, head fusion off so that every block output is stored).  Blocks
+upstream of j keep their own launches, so j's input is what the heuristic plan computed -- checked bit for bit -- and j's
+float64 reference is computed once per case from that input:
+
+  * elementwise  |got - ref64| <= TAU * S, S the same block evaluated on |input| with every weight, bias, folded-BN
+    scale / shift and time-bias term replaced by its magnitude (the sum of the terms' magnitudes at each stage);
+  * per image    relative L2 error against float64 <= REL_L2, and the RMS of err / S <= RMS_C * 2^-24, for every batch row
+    on its own (tail rows of a ragged tile cannot hide in an average);
+  * padding      channels cout .. cout_p of the block output are exactly 0;
+  * poisoning    the workspace and eps are filled with NaN, then with 1e30, before the forward: the block output and eps
+    must come out bit-identical (no launch reads an element that no launch of the forward wrote) and eps finite.
+
+The cases cover the ragged M tiles of 41 images (4x4 / 2x2 / 1x1 levels), the 256 x 64 tiles and the epilogue modes of the
+half-size model, odd channel counts (38 / 51 channels), 32 x 32 pictures (2 x 2 bottleneck), a mixed batch (shared enc1 with
+single-pass images) and a one-pass forward (a pin keyed by the one-pass image split).  Every case runs every launch the
+rules admit (about 8800 in all, twice each: on one MI355X the module takes about 16 s).
+"""
+import math
+import random
+from collections import defaultdict
+from ctypes import byref, c_int, c_size_t
+from typing import NamedTuple
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from distillation_trajectories_amd import _hip, engine
+from distillation_trajectories_amd._hip import COND_NONE, COND_ONE, COND_ZERO, HipLibraryError, check, ptr, stream_ptr
+from oracle import unet_ref
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+# Elementwise bound TAU * S with TAU = C_TAU * 2^-24.  Measured on an MI355X over every launch of every case: max err / S
+# = 0.50 * 2^-24 (fp32 0.42, split-bf16 0.50, strip 0.47, strip32 0.44, stripk 0.40); C_TAU keeps a 4x margin
+C_TAU = 2
+TAU = C_TAU * 2.0 ** -24
+REL_L2 = 1e-6                    # per-image relative L2 error of a block output against float64 (measured max 5.2e-7)
+# per-image RMS of err / S, in units of 2^-24: measured max 0.096 (fp32, split-bf16 GEMM kinds), 0.045 (strip kinds).  Far
+# below the elementwise bound, it sees errors the size of fp32 rounding spread over a whole image, e.g. one of the six
+# plane products of a strip kind dropped (0.29)
+RMS_C = 0.2
+POISONS = (float("nan"), 1e30)   # fmaxf-style ReLUs turn a NaN read into 0: a large finite value is needed too
+KDIV = (1, 2, 4, 8, 16, 8, 4, 2)
+SLOT_NAMES = ("skip", "conv1", "conv2")
+AXES = dict(bm=(64, 128, 256), bn=(64, 128), splits=range(1, 10), kind=range(6), fuse=(0, 1))   # record_launch_rules.GRID_AXES
+SKIP_CONV2 = (64, 64, 1, 1, 0)   # conv2 pinned unfused while the 1x1 skip runs as a launch of its own
+
+
+class Case(NamedTuple):
+    name: str
+    sf: float
+    H: int
+    B: int
+    n_pass: int
+    single: int      # single-pass images of a mixed batch (dt_unet_forward_mixed)
+    tb_div: int
+    min_launches: int   # distinct launches the rules admit (at least)
+    seed: int
+
+
+CASES = (
+    Case("A_sf1.0_16px_B41", 1.0, 16, 41, 2, 0, 41, 1400, 1),
+    Case("B_sf0.5_16px_B41", 0.5, 16, 41, 2, 0, 1, 1200, 2),
+    Case("C_sf0.3_16px_B41", 0.3, 16, 41, 2, 0, 1, 950, 3),
+    Case("C_sf0.4_16px_B41", 0.4, 16, 41, 2, 0, 1, 920, 4),
+    Case("D_sf1.0_32px_B5", 1.0, 32, 5, 2, 0, 1, 1500, 5),
+    Case("E_sf0.5_mixed_B9_single3", 0.5, 16, 9, 2, 3, 1, 1200, 6),
+    Case("F_sf0.5_one_pass_B12", 0.5, 16, 12, 1, 0, 1, 1200, 7),
+)
+
+
+@pytest.fixture(scope="module")
+def cpu_threads():
+    """float64 references on at most 16 threads (a GPU box may show many more cores than a job may use)"""
+    old = torch.get_num_threads()
+    torch.set_num_threads(max(1, min(old, 16)))
+    yield
+    torch.set_num_threads(old)
+
+
+@pytest.fixture(scope="module")
+def stats():
+    """per launch kind: the largest err / S (in units of 2^-24), per-image relative L2 error and per-image RMS of err / S"""
+    table = defaultdict(lambda: [0.0, 0.0, 0.0, 0])
+    yield table
+    print("\nper-kind maxima over all cases: kind: (max err/S [2^-24], max per-image rel L2, max per-image RMS err/S [2^-24], "
+          "variants)")
+    for kind in sorted(table):
+        r, l2, rms, n = table[kind]
+        print(f"  {_hip.KIND_NAMES.get(kind, kind)}: ({r:.3f}, {l2:.3e}, {rms:.4f}, {n})")
+
+
+# ------------------------------------------------------------------ batch rows of a case
+def row_images(c):
+    """image of every batch row: [pass 0 of all images | passes 1.. of images single..B-1]"""
+    return list(range(c.B)) + [b for _ in range(c.n_pass - 1) for b in range(c.single, c.B)]
+
+
+def row_conditions(c):
+    """(t, cond mode) of every time-bias row (row r of the batch uses tb row r // tb_div)"""
+    rows = len(row_images(c)) // c.tb_div
+    rng = random.Random(100 + c.seed)
+    if c.tb_div == c.B:     # one row per pass, the sampler's CFG layout
+        return [(9, COND_NONE), (9, COND_ONE)][:rows]
+    modes = (COND_NONE, COND_ZERO, COND_ONE)
+    return [(rng.randrange(0, 1000), modes[rng.randrange(3)]) for _ in range(rows)]
+
+
+def row_temb(sd32, conds, tb_div):
+    """float64 [rows, D] time embedding of every batch row, evaluated in fp32 as the device's time-bias kernel does"""
+    t = torch.tensor([tc[0] for tc in conds], dtype=torch.long)
+    embs = {COND_NONE: unet_ref.time_embedding(sd32, t, None),
+            COND_ZERO: unet_ref.time_embedding(sd32, t, torch.zeros(len(conds), 1)),
+            COND_ONE: unet_ref.time_embedding(sd32, t, torch.ones(len(conds), 1))}
+    temb = torch.stack([embs[m][i] for i, (_, m) in enumerate(conds)]).double()
+    return temb.repeat_interleave(tb_div, dim=0)
+
+
+# ------------------------------------------------------------------ float64 block and its magnitude bound
+def _folded_bn(sd, name, i):
+    """(scale, magnitude of the folded shift) of conv i + BatchNorm: y = scale * conv + ((bias - mean) * scale + beta)"""
+    scale = sd[f"{name}.norm{i}.weight"] / torch.sqrt(sd[f"{name}.norm{i}.running_var"] + 1e-5)
+    mag = (sd[f"{name}.conv{i}.bias"].abs() + sd[f"{name}.norm{i}.running_mean"].abs()) * scale.abs() + sd[f"{name}.norm{i}.bias"].abs()
+    return scale.abs()[None, :, None, None], mag[None, :, None, None]
+
+
+def block_bound(sd, name, xa, temb):
+    """S: models.py's Block on the input magnitudes xa with every term replaced by its magnitude"""
+    s1, a1 = _folded_bn(sd, name, 1)
+    h = s1 * F.conv2d(xa, sd[name + ".conv1.weight"].abs(), padding=1) + a1
+    h = h + F.linear(temb.abs(), sd[name + ".time_mlp.weight"].abs(), sd[name + ".time_mlp.bias"].abs())[:, :, None, None]
+    s2, a2 = _folded_bn(sd, name, 2)
+    out = s2 * F.conv2d(h, sd[name + ".conv2.weight"].abs(), padding=1) + a2
+    rkey = name + ".residual_conv.weight"
+    return out + (F.conv2d(xa, sd[rkey].abs(), sd[name + ".residual_conv.bias"].abs()) if rkey in sd else xa)
+
+
+def _up(a):
+    return F.interpolate(a, scale_factor=2, mode="bilinear", align_corners=True)
+
+
+def block_references(sd64, x64, acts, temb):
+    """{j: (ref64, S)} of every block, from the device's own outputs of the blocks upstream (acts: float64 NCHW)"""
+    out = {}
+    with torch.no_grad():
+        for j, name in enumerate(engine.BLOCK_NAMES):
+            if j == 0:
+                xin, xa = x64, x64.abs()
+            elif j <= 4:
+                xin = F.max_pool2d(acts[j - 1], 2)
+                xa = xin.abs()
+            else:
+                prev, skip = acts[j - 1], acts[8 - j]
+                xin = torch.cat([_up(prev), skip], 1)
+                xa = torch.cat([_up(prev.abs()), skip.abs()], 1)    # bilinear terms summed by magnitude
+            out[j] = (unet_ref.block_forward(sd64, name, xin, temb), block_bound(sd64, name, xa, temb))
+    return out
+
+
+# ------------------------------------------------------------------ one case on the device
+class Runner:
+    def __init__(self, c, sd32):
+        self.c = c
+        self.h = engine.UNetHandle(sd32, DEV)
+        self.h.set_head_fusion(False)
+        self.h.set_fused(False)
+        self.imgs = row_images(c)
+        self.rows = len(self.imgs)
+        g = torch.Generator().manual_seed(1000 + c.seed)
+        self.x = torch.randn(c.B, 3, c.H, c.H, generator=g)
+        self.x_dev = self.x.to(DEV)
+        self.conds = row_conditions(c)
+        self.tb = self.h.time_bias([t for t, _ in self.conds], [m for _, m in self.conds])
+        self.ws = self.h.workspace(self.rows, c.H, c.H)
+        self.eps = torch.empty(self.rows, 3, c.H, c.H, dtype=torch.float32, device=DEV)
+        self.couts = [sd32[f"{n}.conv2.weight"].shape[0] for n in engine.BLOCK_NAMES]
+
+    # -- library calls
+    def forward(self):
+        """one forward into self.eps / the workspace; returns the library status"""
+        c, h = self.c, self.h
+        with torch.cuda.device(DEV):
+            if c.single:
+                return h.lib.dt_unet_forward_mixed(h.h, ptr(self.x_dev), c.B, c.single, c.H, c.H, ptr(self.tb), c.tb_div,
+                                                   ptr(self.eps), ptr(self.ws), c_size_t(self.ws.numel()), stream_ptr())
+            return h.lib.dt_unet_forward(h.h, ptr(self.x_dev), c.B, c.n_pass, c.H, c.H, ptr(self.tb), c.tb_div, ptr(self.eps),
+                                         ptr(self.ws), c_size_t(self.ws.numel()), stream_ptr())
+
+    def poisoned_forward(self, value):
+        self.ws.view(torch.float32).fill_(value)
+        self.eps.fill_(value)
+        return self.forward()
+
+    def act(self, j):
+        return self.h.debug_activation(self.rows, self.c.H, self.c.H, j)
+
+    def report(self, j, slot):
+        v = [c_int() for _ in range(5)]
+        check(self.h.lib.dt_unet_conv_choice(self.h.h, self.rows, self.c.H, self.c.H, j, slot, *map(byref, v)), "dt_unet_conv_choice")
+        return tuple(x.value for x in v)
+
+    def pin(self, j, slot, bm, bn, splits, kind, fuse):
+        """fresh heuristic plan + one pinned slot (slot 0: conv2 pinned unfused first); False where the library refuses"""
+        h, c = self.h, self.c
+        h.set_precision(_hip.PREC_AUTO)
+        try:
+            if slot == 0:
+                h.set_conv_choice(self.rows, c.H, c.H, j, 2, *SKIP_CONV2, images=c.B, single=c.single)
+            h.set_conv_choice(self.rows, c.H, c.H, j, slot, bm, bn, splits, kind, fuse, images=c.B, single=c.single)
+        except HipLibraryError:
+            return False
+        return True
+
+    # -- the launch vocabulary
+    def admissible(self):
+        """{(j, slot, resolved report [bm, bn, splits, kind + 8 fuse]): request} over the whole vocabulary"""
+        found = {}
+        for j in range(8):
+            for slot in range(3):
+                for bm in AXES["bm"]:
+                    for bn in AXES["bn"]:
+                        for sp in AXES["splits"]:
+                            for kind in AXES["kind"]:
+                                for fuse in AXES["fuse"]:
+                                    if fuse and slot != 2:
+                                        continue
+                                    if not self.pin(j, slot, bm, bn, sp, kind, fuse):
+                                        continue
+                                    rep = self.report(j, slot)
+                                    if rep[0] == 0:
+                                        continue         # no launch of its own (enc1's first conv / skip, identity skips)
+                                    found.setdefault((j, slot) + rep[:4], (bm, bn, sp, kind, fuse))
+        self.h.set_precision(_hip.PREC_AUTO)
+        return found
+
+
+def expected_kinds(c, j, slot):
+    """launch kinds the rules admit for a slot: the strip kinds need a full 3x3 walk (not a 1x1 conv or a 1x1 picture)"""
+    side = c.H // KDIV[j]
+    return {0, 1} if slot == 0 or side == 1 else {0, 1, 3, 4, 5}
+
+
+def check_block(got, ref, S, cout):
+    """[any elementwise failure, max err/S, max per-image rel L2, any nonzero padding, max per-image RMS of err/S] as one
+    device tensor"""
+    g = got[..., :cout].permute(0, 3, 1, 2).double()
+    err = (g - ref).abs()
+    bad = ~(err <= TAU * S + 1e-30)
+    q = torch.nan_to_num(err / S.clamp_min(1e-300), nan=math.inf)
+    rel = torch.nan_to_num((g - ref).flatten(1).norm(dim=1) / ref.flatten(1).norm(dim=1).clamp_min(1e-300), nan=math.inf).amax()
+    rms = q.flatten(1).square().mean(dim=1).sqrt().amax()
+    pad = (got[..., cout:] != 0).any() if got.shape[-1] > cout else torch.zeros((), dtype=torch.bool, device=got.device)
+    return torch.stack([bad.any().double(), q.amax(), rel, pad.double(), rms])
+
+
+def bits(t):
+    return t.contiguous().view(torch.int32)
+
+
+def run_case(c, models, stats):
+    sd32 = {k: v.float() for k, v in models(c.sf).state_dict().items() if v.dtype.is_floating_point}
+    sd64 = {k: v.double() for k, v in sd32.items()}
+    run = Runner(c, sd32)
+    h, rows = run.h, run.rows
+
+    if c.name.startswith("F_"):
+        # the pin of a one-pass shape made before its first forward is the one the forward runs (the library would otherwise
+        # key it by the two-pass split images = rows / 2)
+        ref_j, ref_slot = 2, 1
+        h.set_conv_choice(rows, c.H, c.H, ref_j, ref_slot, 64, 64, 1, _hip.KIND_FP32, 0, images=c.B)
+        h.forward(run.x_dev, run.tb, c.n_pass, c.tb_div)
+        rep = run.report(ref_j, ref_slot)
+        assert rep == (64, 64, 1, _hip.KIND_FP32, 1), f"pin before the first one-pass forward was dropped: report {rep}"
+        assert set(h.plan_ids().values()) == {"pinned"}, h.plan_ids()
+        h.set_precision(_hip.PREC_AUTO)            # drops the pins: the next forward settles its own plan
+        h.forward(run.x_dev, run.tb, c.n_pass, c.tb_div)
+        assert "pinned" not in h.plan_ids().values() and run.report(ref_j, ref_slot)[4] == 0, h.plan_ids()
+    h.ensure_plan(rows, c.H, c.H, c.B, c.single, tune=False)
+
+    # the heuristic plan's block outputs: the inputs of the references, and what every pinned forward must leave upstream
+    h.set_precision(_hip.PREC_AUTO)
+    base = []
+    for value in POISONS:
+        check(run.poisoned_forward(value), "dt_unet_forward")
+        base.append(([run.act(j).clone() for j in range(8)], run.eps.clone()))
+    for j in range(8):
+        assert torch.equal(bits(base[0][0][j]), bits(base[1][0][j])), f"{c.name}: heuristic plan, {engine.BLOCK_NAMES[j]} reads unwritten memory"
+    assert torch.equal(bits(base[0][1]), bits(base[1][1])) and torch.isfinite(base[0][1]).all(), f"{c.name}: heuristic plan, eps"
+    acts = [a[..., :cout].permute(0, 3, 1, 2).double().cpu() for a, cout in zip(base[0][0], run.couts)]
+    x64 = run.x.double()[run.imgs]
+    temb = row_temb(sd32, run.conds, c.tb_div)
+    refs = {j: (r.to(DEV), s.to(DEV)) for j, (r, s) in block_references(sd64, x64, acts, temb).items()}
+
+    found = run.admissible()
+    admitted = defaultdict(set)
+    for key in found:
+        admitted[key[:2]].add(key[5] & 7)
+    for (j, slot), kinds in admitted.items():
+        assert kinds == expected_kinds(c, j, slot), f"{c.name}: {engine.BLOCK_NAMES[j]}.{SLOT_NAMES[slot]} admits kinds {sorted(kinds)}"
+    assert len(found) >= c.min_launches, f"{c.name}: the rules admit only {len(found)} distinct launches"
+
+    failures, ran, refused, seen = [], 0, [], defaultdict(set)
+    for key in [None] + sorted(found):
+        if key is None:                       # the heuristic plan itself
+            j, slot, what = None, None, "heuristic plan"
+            h.set_precision(_hip.PREC_AUTO)
+        else:
+            j, slot = key[:2]
+            req = found[key]
+            what = f"{engine.BLOCK_NAMES[j]}.{SLOT_NAMES[slot]} {_hip.KIND_NAMES[key[5] & 7]} {key[2]}x{key[3]} s{key[4]}" \
+                   f"{' +skip' if key[5] & 8 else ''} (kind {key[5] & 7}, request {req})"
+            assert run.pin(j, slot, *req), what
+            assert run.report(j, slot)[:4] == key[2:], f"{what}: resolves differently on a second pin"
+        outs, flags = [], []
+        status = 0
+        for value in POISONS:
+            status = run.poisoned_forward(value)
+            if status < 0:
+                break
+            check(status, f"dt_unet_forward ({what})")
+            blocks = range(8) if j is None else [j]
+            outs.append(([run.act(b).clone() for b in blocks], run.eps.clone()))
+            if j is not None:
+                flags += [(bits(run.act(u)) != bits(base[0][0][u])).any() for u in range(j)]
+        if status < 0:
+            refused.append(key)               # the launcher refuses a choice the rules resolve to (e.g. its LDS or reach)
+            continue
+        if key is not None:
+            rep = run.report(j, slot)
+            if rep[:4] != key[2:] or rep[4] != 1:
+                failures.append(f"{what}: the report after the forward shows {rep}, not the pin")
+        ran += 1
+        for b_idx, b in enumerate(range(8) if j is None else [j]):
+            ref, S = refs[b]
+            res = check_block(outs[0][0][b_idx], ref, S, run.couts[b])
+            differs = (bits(outs[0][0][b_idx]) != bits(outs[1][0][b_idx])).any()
+            bad, ratio, rel, pad, rms = res.tolist()
+            kind = key[5] & 7 if key is not None else None
+            where = what if key is not None else f"{what}, {engine.BLOCK_NAMES[b]}"
+            if differs.item():
+                failures.append(f"{where}: block output differs between NaN- and 1e30-poisoned workspaces")
+            if bad:
+                failures.append(f"{where}: |err| > {C_TAU} * 2^-24 * S (max err/S = {ratio * 2 ** 24:.2f} * 2^-24)")
+            if rel > REL_L2:
+                failures.append(f"{where}: per-image relative L2 error {rel:.3e} > {REL_L2:.0e}")
+            if rms * 2 ** 24 > RMS_C:
+                failures.append(f"{where}: per-image RMS of err/S {rms * 2 ** 24:.3f} * 2^-24 > {RMS_C} * 2^-24")
+            if pad:
+                failures.append(f"{where}: nonzero padding channels")
+            if kind is not None:
+                st = stats[kind]
+                st[0], st[1], st[2], st[3] = max(st[0], ratio * 2 ** 24), max(st[1], rel), max(st[2], rms * 2 ** 24), st[3] + 1
+                seen[(j, slot)].add(kind)
+        if not torch.equal(bits(outs[0][1]), bits(outs[1][1])) or not torch.isfinite(outs[0][1]).all():
+            failures.append(f"{what}: eps differs between poisons or is not finite")
+        if flags and torch.stack(flags).any().item():
+            failures.append(f"{what}: a block upstream of the pinned one changed")
+
+    # head fusion on (the default): the heuristic plan's stored block outputs are bit-identical to the head-off run, eps agrees
+    h.set_head_fusion(True)
+    h.set_precision(_hip.PREC_AUTO)
+    fused = []
+    for value in POISONS:
+        check(run.poisoned_forward(value), "dt_unet_forward (head fusion on)")
+        fused.append(([run.act(j).clone() for j in range(8)], run.eps.clone()))
+    h.set_head_fusion(False)
+    assert torch.equal(bits(fused[0][1]), bits(fused[1][1])) and torch.isfinite(fused[0][1]).all(), f"{c.name}: head fusion on, eps"
+    for j in range(8):
+        a = fused[0][0][j]
+        if j in (0, 7) and torch.isnan(a).all():
+            continue                           # not stored with head fusion on: enc1 under skip_out, dec1 under the fused head
+        assert torch.equal(bits(a), bits(base[0][0][j])), f"{c.name}: head fusion on changes {engine.BLOCK_NAMES[j]}"
+    e_on, e_off = fused[0][1].double(), base[0][1].double()
+    rel_eps = ((e_on - e_off).flatten(1).norm(dim=1) / e_off.flatten(1).norm(dim=1)).max().item()
+    assert rel_eps <= REL_L2, f"{c.name}: eps with the fused head differs by {rel_eps:.3e} (relative L2, worst row)"
+
+    print(f"\n{c.name}: {len(found)} admissible launches, {ran - 1} run, refused at launch: {refused}, head-fused eps "
+          f"{'bit-identical' if torch.equal(fused[0][1], base[0][1]) else f'rel L2 {rel_eps:.2e}'}")
+    assert not failures, f"{c.name}: {len(failures)} failures:\n  " + "\n  ".join(failures[:40])
+    # the one choice the rules admit and the launcher refuses: stripk's 64 x 64 tile (one strip item per thread) on rows of
+    # more than 31 pixels
+    for j, slot, bm, bn, _, kind in refused:
+        assert (kind & 7, bm, bn) == (5, 64, 64) and c.H // KDIV[j] > 31, f"{c.name}: launch {(j, slot, bm, bn, kind)} refused"
+    for (j, slot), kinds in admitted.items():
+        assert seen[(j, slot)] == kinds, f"{c.name}: {engine.BLOCK_NAMES[j]}.{SLOT_NAMES[slot]} ran kinds {sorted(seen[(j, slot)])} of {sorted(kinds)}"
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c.name for c in CASES])
+def test_conv_launches_block_by_block_vs_float64(case, models, cpu_threads, stats):
+    run_case(case, models, stats)
+
+
+# ------------------------------------------------------------------ more than two condition rows per image
+@pytest.mark.parametrize("sf,shared", [(0.1, True), (0.2, True), (0.5, True), (0.5, False)],
+                         ids=["sf0.1-fused", "sf0.2-fused", "sf0.5-shared-enc1", "sf0.5-per-pass-enc1"])
+@pytest.mark.parametrize("n_pass", [3, 4])
+def test_forward_with_three_and_four_passes(models, monkeypatch, sf, shared, n_pass):
+    """dt_unet_forward accepts any n_pass (e.g. cond rows NONE / ZERO / ONE): the fused small-model kernel, enc1 shared by
+    all passes (n_dup = n_pass) and one enc1 per pass, every row against the oracle"""
+    if not shared:
+        monkeypatch.setenv("DT_NO_SHARED_ENC1", "1")     # read by dt_unet_create
+    sd = {k: v.float() for k, v in models(sf).state_dict().items()}
+    h = engine.UNetHandle(sd, DEV)
+    monkeypatch.delenv("DT_NO_SHARED_ENC1", raising=False)
+    assert h.fused_active(16, 16) == (sf < 0.3) and h._shared_enc1 == shared
+    B = 5
+    x = torch.randn(B, 3, 16, 16, generator=torch.Generator().manual_seed(40 + n_pass))
+    ts = [3, 17, 29, 40][:n_pass]
+    modes = [COND_NONE, COND_ZERO, COND_ONE, COND_ONE][:n_pass]
+    got = h.forward(x.to(DEV), h.time_bias(ts, modes), n_pass, B).cpu().numpy()
+    assert got.shape == (n_pass * B, 3, 16, 16)
+    for p, (t, m) in enumerate(zip(ts, modes)):
+        cond = None if m == COND_NONE else torch.full((B, 1), 0.0 if m == COND_ZERO else 1.0)
+        with torch.no_grad():
+            want = unet_ref.unet_forward(sd, x, torch.full((B,), t), cond).numpy()
+        err = np.abs(got[p * B:(p + 1) * B] - want)
+        tol = 2e-5 + 1e-4 * np.abs(want)
+        assert np.all(err <= tol), f"sf {sf} n_pass {n_pass} pass {p}: max err {err.max():.3e}"
