@@ -82,6 +82,20 @@ NOISE_SIGNATURES = {
     "dt_q_sample": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
 }
 
+# name -> (restype, argtypes) of every symbol include/dt_hip_inception.h declares (the FID feature extractor)
+INCEPTION_SIGNATURES = {
+    "dt_inception_conv_desc": (c_int, [c_int, POINTER(c_int)]),
+    "dt_inception_module_shape": (c_int, [c_int, POINTER(c_int), POINTER(c_int)]),
+    "dt_inception_create": (c_int, [POINTER(c_void_p), c_int, c_void_p, POINTER(c_void_p)]),
+    "dt_inception_destroy": (None, [c_void_p]),
+    "dt_inception_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "dt_inception_preprocess": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p]),
+    "dt_inception_features": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_void_p,
+                                      c_void_p, c_size_t, c_void_p]),
+    "dt_inception_run_modules": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t,
+                                         c_void_p]),
+}
+
 
 def load(path=None):
     """Load (once) and return the library with argtypes set.  Raises HipLibraryError if absent."""
@@ -98,7 +112,7 @@ def load(path=None):
         lib = ctypes.CDLL(path)
     except OSError as e:
         raise HipLibraryError(f"cannot load {path}: {e}. There is no CPU fallback.") from e
-    for name, (res, args) in {**SIGNATURES, **NOISE_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **NOISE_SIGNATURES, **INCEPTION_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -6,14 +6,20 @@ with beta_t = beta_start + (beta_end-beta_start)*t/T and a running-product alpha
 MANAGER rule, so it runs device-resident with per-step coefficients computed on the host the way the
 reference computes them (python floats -> fp32 0-dim tensors).  ``generate_samples`` batches all samples into
 one loop (the reference runs them one by one); noise is drawn from the CPU generator in the reference's
-order.  ``calculate_fid`` is the reference's numpy/scipy formula.  The InceptionV3 feature extractor needs
-pretrained weights that cannot be fetched offline and is not provided.
+order.  ``calculate_fid`` is the reference's numpy/scipy formula.
+
+The InceptionV3 features (reference :19-56) run on the device (``inception.InceptionHandle``, include/dt_hip_inception.h)
+with the user's copy of torchvision's pretrained weights (``weights=`` or ``DT_INCEPTION_WEIGHTS``; never downloaded).
+``calculate_and_visualize_fid`` is the reference's driver (:96-198) without the figure.
 """
+import os
+
 import numpy as np
 import torch
 from scipy import linalg
 
 from ... import engine
+from ... import inception
 from ..._hip import COND_NONE, RULE_MANAGER
 
 
@@ -96,3 +102,61 @@ def generate_samples(model, config, num_samples, device, fixed_samples=None):
     x0 = torch.cat(starts)
     z = torch.stack(zs, dim=1).reshape(T - 1, n, -1) if T > 1 else None
     return _run(model, x0, config, z)
+
+
+class InceptionModel:
+    """Reference :19-56: ``get_features(images)`` -> [N, 2048] numpy features of images in [-1, 1] (mapped by
+    (x + 1) / 2, resized to 299 x 299 and normalised with ImageNet's mean / std), in batches of 32 as the reference
+    runs them.  ``weights`` is a path or a state dict of torchvision's Inception3 (default: ``$DT_INCEPTION_WEIGHTS``)."""
+
+    def __init__(self, device, weights=None):
+        self.device = torch.device(device)
+        self.handle = inception.InceptionHandle(inception.read_weights(weights), self.device)
+
+    def get_features(self, images):
+        return extract_features(images, self, batch_size=32, in_scale=0.5, in_shift=0.5).cpu().numpy()
+
+
+def extract_features(images, model=None, weights=None, device=None, batch_size=64, in_scale=1.0, in_shift=0.0):
+    """[N, 2048] fp32 features on the device for images [N, 3, H, W] (1 <= H, W <= 299), ``batch_size`` images per
+    launch sequence.  ``in_scale * x + in_shift`` is applied first: (0.5, 0.5) is get_features' (x + 1) / 2, the default
+    (1, 0) takes the images as given (compute_fid).  An image's features do not depend on the batching.  ``model`` is
+    an InceptionModel; without one, one is built on ``device`` (default cuda) from ``weights``."""
+    inception.check_images(images)
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+    if model is None:
+        model = InceptionModel(device if device is not None else (images.device if images.is_cuda else "cuda"), weights)
+    h = model.handle
+    out = torch.empty(len(images), inception.N_FEATURES, dtype=torch.float32, device=h.device)
+    for i in range(0, len(images), batch_size):
+        h.features(images[i:i + batch_size], in_scale, in_shift, out=out[i:i + batch_size])
+    return out
+
+
+def calculate_and_visualize_fid(teacher_model, student_model, config, output_dir=None, size_factor=None,
+                                fixed_samples=None, weights=None):
+    """Reference :96-198: FID between teacher and student samples; console lines, ``fid_score_size_{sf}.txt`` and the
+    returned ``{"fid_score": ...}`` as the reference's.  No figure is drawn."""
+    if output_dir is None:
+        output_dir = os.path.join(config.analysis_dir, "fid", f"size_{size_factor}")
+    os.makedirs(output_dir, exist_ok=True)
+    print(f"Calculating FID scores for size factor {size_factor}...")
+    device = next(teacher_model.parameters()).device
+    teacher_model.eval()
+    student_model.eval()
+    num_samples = config.num_samples if hasattr(config, 'num_samples') else 50
+    print("  Generating samples from teacher model...")
+    teacher_samples = generate_samples(teacher_model, config, num_samples, device, fixed_samples=fixed_samples)
+    print("  Generating samples from student model...")
+    student_samples = generate_samples(student_model, config, num_samples, device, fixed_samples=fixed_samples)
+    print("  Extracting features using InceptionV3...")
+    inception_model = InceptionModel(device, weights)
+    teacher_features = inception_model.get_features(teacher_samples)
+    student_features = inception_model.get_features(student_samples)
+    print("  Calculating FID score...")
+    fid_score = calculate_fid(teacher_features, student_features)
+    print(f"  FID score for size factor {size_factor}: {fid_score:.4f}")
+    with open(os.path.join(output_dir, f"fid_score_size_{size_factor}.txt"), "w") as f:
+        f.write(f"FID Score: {fid_score:.4f}\n")
+    return {"fid_score": fid_score}

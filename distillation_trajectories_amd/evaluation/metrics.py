@@ -1,15 +1,40 @@
-"""Trajectory divergence (reference evaluation/metrics.py:118-183) on the HIP metric kernels.
+"""Trajectory divergence (reference evaluation/metrics.py:118-183) on the HIP metric kernels, and FID (:51-116).
 
-Only ``compute_trajectory_divergence`` is provided: LPIPS and FID in the reference's module need
-pretrained networks that cannot be fetched offline.  Distances, cosine
-similarities and path lengths come from two device reductions (dt_pair_stats, dt_traj_metrics) over the
-stacked trajectories instead of 3 x len python loops of ``torch.norm(...).item()`` / sklearn calls.
+Distances, cosine similarities and path lengths come from two device reductions (dt_pair_stats, dt_traj_metrics)
+over the stacked trajectories instead of 3 x len python loops of ``torch.norm(...).item()`` / sklearn calls.
+``compute_fid`` runs the InceptionV3 features on the device with user-supplied weights (``weights=`` or
+``DT_INCEPTION_WEIGHTS``).  LPIPS is not provided: it needs a pretrained network of its own.
 """
 import numpy as np
 import torch
+from scipy.linalg import sqrtm
 
 from .. import engine
+from ..analysis.metrics.fid_score import InceptionModel, extract_features
 from ..analysis.metrics.trajectory_metrics import _metrics_device, _stack_on_device
+
+
+def _as_batch(images):
+    return torch.cat(list(images)) if isinstance(images, (list, tuple)) else images
+
+
+def compute_fid(real_images, generated_images, device, batch_size=8, weights=None):
+    """Reference :51-116: FID between two image sets (lists of [1, 3, H, W] tensors, or [N, 3, H, W] tensors), taken
+    as given (no (x + 1) / 2), with the reference's arithmetic.  ``weights``: torchvision's Inception3 state dict or
+    its path (default ``$DT_INCEPTION_WEIGHTS``)."""
+    real, gen = _as_batch(real_images), _as_batch(generated_images)
+    inception = InceptionModel(device, weights)
+    real_features = extract_features(real, inception, batch_size=batch_size).cpu().numpy()
+    gen_features = extract_features(gen, inception, batch_size=batch_size).cpu().numpy()
+    mu_real = np.mean(real_features, axis=0)
+    sigma_real = np.cov(real_features, rowvar=False)
+    mu_gen = np.mean(gen_features, axis=0)
+    sigma_gen = np.cov(gen_features, rowvar=False)
+    diff = mu_real - mu_gen
+    covmean = sqrtm(sigma_real.dot(sigma_gen))
+    if np.iscomplexobj(covmean):
+        covmean = covmean.real
+    return diff.dot(diff) + np.trace(sigma_real + sigma_gen - 2 * covmean)
 
 
 def compute_trajectory_divergence(trajectory1, trajectory2):
