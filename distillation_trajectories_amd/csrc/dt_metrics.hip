@@ -152,6 +152,9 @@ int launch_sample_mean(const float *traj, int n, int B, int E, float *out, hipSt
 // W1 between the empirical distributions of the coordinates of X_i and Y_i (equal sample sizes):
 // mean_k |u_(k) - v_(k)| over the order statistics.  Both samples are bitonic-sorted in LDS
 // (padded to a power of two with +inf, which sorts to the tail of BOTH arrays and cancels).
+// A NaN has no place in that order: the float compare-exchange moves it on every descending stage,
+// and it can end in the padding while a +inf pad takes its slot inside the counted range (W1 = +inf
+// where scipy gives NaN).  So a NaN coordinate is flagged while loading and makes the step's W1 NaN.
 template <int N>
 __device__ inline void bitonic_sort(float *a) {
   for (int k = 2; k <= N; k <<= 1) {
@@ -178,9 +181,10 @@ __global__ __launch_bounds__(256) void wasserstein_kernel(const float *__restric
   const float *x = X + ((size_t)i * B + b) * E, *y = Y + ((size_t)i * B + b) * E;
   const int cnt = index ? n_idx : E;
   const int32_t *idx = index ? index + ((size_t)(index_row ? index_row[b] : 0) * n + i) * n_idx : nullptr;
+  bool has_nan = false;
   for (int k = threadIdx.x; k < N; k += blockDim.x) {
     float a = __builtin_inff(), c = __builtin_inff();
-    if (k < cnt) { const int e = idx ? idx[k] : k; a = x[e]; c = y[e]; }
+    if (k < cnt) { const int e = idx ? idx[k] : k; a = x[e]; c = y[e]; has_nan |= (a != a) || (c != c); }
     u[k] = a; v[k] = c;
   }
   __syncthreads();
@@ -188,6 +192,7 @@ __global__ __launch_bounds__(256) void wasserstein_kernel(const float *__restric
   bitonic_sort<N>(v);
   double acc[1] = {0.0};
   for (int k = threadIdx.x; k < cnt; k += blockDim.x) acc[0] += fabs((double)u[k] - (double)v[k]);
+  if (has_nan) acc[0] = __builtin_nan("");
   block_sum<1>(acc, sm);
   if (threadIdx.x == 0) out[(size_t)b * n + i] = acc[0] / (double)cnt;
 }

@@ -482,10 +482,19 @@ def unet_forward_module(module, x, t, cond=None):
 
 
 # ---------------------------------------------------------------------- metrics
+def _pad_quads(t):
+    """t [n, B, E] with the coordinate axis zero-padded to a multiple of 4: dt_traj_metrics and dt_pair_stats load float4
+    quads and take E % 4 == 0 only.  Padding BOTH operands with zeros adds exactly 0 to every one of their sums (endpoint
+    rows included); the Wasserstein and resampled-distance kernels take any E and get the unpadded tensors."""
+    E = t.shape[-1]
+    return t if E % 4 == 0 else torch.nn.functional.pad(t, (0, -E % 4)).contiguous()
+
+
 def device_metric_sums(X, Y):
-    """float64 [B, n_max, 4] sums of dt_traj_metrics for trajectories X[nT,B,E], Y[nS,B,E] on device."""
+    """float64 [B, n_max, 4] sums of dt_traj_metrics for trajectories X[nT,B,E], Y[nS,B,E] on device (any E)."""
     lib = _hip.load()
     _require_cuda(X, "teacher trajectory"); _require_cuda(Y, "student trajectory")
+    X, Y = _pad_quads(X), _pad_quads(Y)
     nT, B, E = X.shape
     nS = Y.shape[0]
     out = torch.empty(B, max(nT, nS), 4, dtype=torch.float64, device=X.device)
@@ -525,9 +534,10 @@ def device_pair_metrics(X, Y, index=None, index_row=None):
 
 
 def device_pair_stats(X, Y):
-    """float64 [B, n, 5] = {sum (x-y)^2, sum |x-y|, sum xy, sum x^2, sum y^2} for X, Y [n, B, E] (dt_pair_stats)."""
+    """float64 [B, n, 5] = {sum (x-y)^2, sum |x-y|, sum xy, sum x^2, sum y^2} for X, Y [n, B, E] (dt_pair_stats, any E)."""
     lib = _hip.load()
     _require_cuda(X, "X"); _require_cuda(Y, "Y")
+    X, Y = _pad_quads(X), _pad_quads(Y)
     n, B, E = X.shape
     out = torch.empty(B, n, 5, dtype=torch.float64, device=X.device)
     with torch.cuda.device(X.device):

@@ -230,14 +230,19 @@ int dt_sample_trajectory_mixed(const dt_unet *h, int rule, int B, int B_single, 
  *   i >= 1: { |X_i-Y_i|^2, |X_i-X_{i-1}|^2, |Y_i-Y_{i-1}|^2, <X_i-X_{i-1}, Y_i-Y_{i-1}> }
  *   i == 0: { |X_0-Y_0|^2, |X_last-X_0|^2, |Y_last-Y_0|^2, |X_last-Y_last|^2 }  (own last states)
  * terms that need a state beyond a trajectory's own length are 0.  The reference's norms run over
- * the whole [B,C,H,W] list entry: for a batched entry call with B=1 and E=B*C*H*W (same memory). */
+ * the whole [B,C,H,W] list entry: for a batched entry call with B=1 and E=B*C*H*W (same memory).
+ * E must be a multiple of 4 (float4 loads; the same holds for dt_pair_stats): callers zero-pad BOTH trajectories, which
+ * adds exactly 0 to every sum. */
 int dt_traj_metrics(const float *teacher_dev, const float *student_dev, int nT, int nS, int B, int E,
                     double *out_sums_dev, void *stream);
 
 /* trajectory_metrics.py:295-315: W1 between the (sub-sampled) value distributions of X_i and Y_i,
  * = mean |sort(u) - sort(v)| accumulated in float64.  index_dev: [n_tables][n][n_idx] int32 coordinates
  * to sample (NULL: use all E coordinates, requires E <= 4096); pair b uses table index_row_dev[b]
- * (NULL: table 0) -- the reference's indices depend on the sample seed only.  out_w1_dev[B][n] float64. */
+ * (NULL: table 0) -- the reference's indices depend on the sample seed only.  out_w1_dev[B][n] float64.
+ * Non-finite samples give scipy.stats.wasserstein_distance's class: a NaN among the sampled coordinates of
+ * X_i or Y_i makes W1 NaN (it is flagged while loading, not left to the sort); an infinity in one sample only
+ * gives +inf; the same infinity in both gives NaN.  dt_traj_pair_metrics follows the same rule. */
 int dt_traj_wasserstein(const float *teacher_dev, const float *student_dev, int n, int B, int E,
                         const int32_t *index_dev, const int32_t *index_row_dev, int n_idx,
                         double *out_w1_dev, void *stream);

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import metrics_ref64 as ref64
 from distillation_trajectories_amd import _hip, engine
 from distillation_trajectories_amd.config import Config
 from distillation_trajectories_amd.models import DiffusionUNet
@@ -487,6 +488,11 @@ def test_one_pass_pair_metrics_keep_non_finite_states_in_their_cell():
     sums, w1 = engine.device_pair_metrics(X.to(DEV), Y.to(DEV))
     ref_s, ref_w = engine.device_metric_sums(X.to(DEV), Y.to(DEV)), engine.device_wasserstein(X.to(DEV), Y.to(DEV))
     assert torch.equal(torch.isfinite(sums), torch.isfinite(ref_s))
+    # the exact class (NaN, +inf, -inf, finite) of every cell, both paths, against the float64 restatement
+    want_s, _ = ref64.traj_metrics(X.numpy(), Y.numpy())
+    want_w, _ = ref64.wasserstein(X.numpy(), Y.numpy())
+    for got, want in ((sums, want_s), (ref_s, want_s), (w1, want_w), (ref_w, want_w)):
+        assert np.array_equal(ref64.classes(got.cpu().numpy()), ref64.classes(want))
     bad = ~torch.isfinite(w1)
     assert torch.equal(bad, ~torch.isfinite(ref_w)) and bad[1, 2] and bad[3, 4] and bad.sum().item() == 2
     ok = torch.isfinite(ref_s)
