@@ -21,13 +21,12 @@
 
 namespace dt {
 
-// ABL != 0 builds are timing experiments (tools/ablate.py) and produce wrong results by design:
-// 1 no barrier, 2 no LDS fragment reads after the first chunk, 3 no MFMA, 4 no global loads, 5 no split VALU
-// Wave layout: WM x WN waves (64*WM*WN threads) tile the BM x BN block; each wave owns (BM/WM) x (BN/WN).
-// Only 2x2 waves of <= 64x64 are instantiated: 256-row tiles (2x4 waves of 128x64, 4x2 of 64x64, 2x2 of 128x64)
-// were measured at 81 / 145 / 103 TF/s against 179 for 128x128 and are not built.
-template <int BM, int BN, int ABL = 0, int WM = 2, int WN = 2>
-__global__ __launch_bounds__(64 * WM * WN, BM * BN > 128 * 128 ? 2 : 3) void conv_gemm_bf16x6_kernel(const ConvParams p) {
+// Wave layout: 2 x 2 waves tile the BM x BN block; each wave owns (BM/2) x (BN/2), at most 64 x 64.  256-row tiles
+// (2x4 waves of 128x64, 4x2 of 64x64, 2x2 of 128x64) were measured at 81 / 145 / 103 TF/s against 179 for 128x128
+//  and are not built.
+template <int BM, int BN>
+__global__ __launch_bounds__(256, BM * BN > 128 * 128 ? 2 : 3) void conv_gemm_bf16x6_kernel(const ConvParams p) {
+  constexpr int WM = 2, WN = 2;                                   // 2x2 waves
   constexpr int MI = BM / (32 * WM), NI = BN / (32 * WN);
   constexpr int PLANE_A = BM * 16, PLANE_B = BN * 16;            // bf16 elements per plane per stage
   constexpr int STAGE = 3 * (PLANE_A + PLANE_B);                  // bf16 elements per stage
@@ -92,11 +91,7 @@ __global__ __launch_bounds__(64 * WM * WN, BM * BN > 128 * 128 ? 2 : 3) void con
     u32x4 rb[BP][3];
 #pragma unroll
     for (int i = 0; i < AP; ++i) { ra0[i] = f32x4{0.f, 0.f, 0.f, 0.f}; ra1[i] = ra0[i]; }
-    if (ABL == 4) {
-      ra0[0] = f32x4{1.f, 2.f, 3.f, 4.f}; ra1[0] = ra0[0];
-      rb[0][0] = rb[0][1] = rb[0][2] = u32x4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};
-      if (more && ++cc == CC) { cc = 0; ++tap; }
-    } else if (more && it + 1 >= n_main) {
+    if (more && it + 1 >= n_main) {
       const int c2 = it + 1 - n_main;
 #pragma unroll
       for (int i = 0; i < AP; ++i)
@@ -137,26 +132,21 @@ __global__ __launch_bounds__(64 * WM * WN, BM * BN > 128 * 128 ? 2 : 3) void con
       if (it == n_main && p.in2) conv_midpoint<MI, NI>(p, acc, n0, wn, l31);
       const __bf16 *A = lds + (it & 1) * STAGE, *B = A + 3 * PLANE_A;
       bf16x8 fb[NI][3];
-      u32x4 fake = {(unsigned)lane * 0x01010101u, 0x3f803f80u, (unsigned)it, 0x3c003c00u};   // ABL == 2 only
 #pragma unroll
       for (int ni = 0; ni < NI; ++ni)
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl)
-          fb[ni][pl] = ABL == 2 ? __builtin_bit_cast(bf16x8, fake) : *reinterpret_cast<const bf16x8 *>(B + pl * PLANE_B + b_frag[ni]);
+          fb[ni][pl] = *reinterpret_cast<const bf16x8 *>(B + pl * PLANE_B + b_frag[ni]);
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi) {
         bf16x8 fa[3];
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl)
-          fa[pl] = ABL == 2 ? __builtin_bit_cast(bf16x8, fake) : *reinterpret_cast<const bf16x8 *>(A + pl * PLANE_A + a_frag[mi]);
+          fa[pl] = *reinterpret_cast<const bf16x8 *>(A + pl * PLANE_A + a_frag[mi]);
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni) {
           // smallest terms first so their sum is formed before it meets the large partial sums
           f32x16 c = acc[mi][ni];
-          if (ABL == 3) {              // keep the fragments live, skip the matrix work
-            asm volatile("" :: "v"(fa[0]), "v"(fa[1]), "v"(fa[2]), "v"(fb[ni][0]), "v"(fb[ni][1]), "v"(fb[ni][2]));
-            continue;
-          }
           c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[2], fb[ni][0], c, 0, 0, 0);
           c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[ni][1], c, 0, 0, 0);
           c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[ni][2], c, 0, 0, 0);
@@ -173,9 +163,6 @@ __global__ __launch_bounds__(64 * WM * WN, BM * BN > 128 * 128 ? 2 : 3) void con
       for (int i = 0; i < AP; ++i)
         if (tid + i * NT < BM * 2) {
           bf16x8 p1, p2, p3;
-          if (ABL == 5) {                // no split VALU: park raw bits
-            p1 = __builtin_bit_cast(bf16x8, ra0[i]); p2 = __builtin_bit_cast(bf16x8, ra1[i]); p3 = p1;
-          } else
           split8(ra0[i], ra1[i], p1, p2, p3);
           *reinterpret_cast<bf16x8 *>(A + a_lds[i]) = p1;
           *reinterpret_cast<bf16x8 *>(A + PLANE_A + a_lds[i]) = p2;
@@ -188,7 +175,7 @@ __global__ __launch_bounds__(64 * WM * WN, BM * BN > 128 * 128 ? 2 : 3) void con
           for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<u32x4 *>(B + pl * PLANE_B + (tid + i * NT) * 8) = rb[i][pl];
         }
     }
-    if (ABL != 1) __syncthreads();
+    __syncthreads();
   }
   static_assert(2 * STAGE * sizeof(__bf16) >= epilogue_stage_floats<BN>() * sizeof(float), "epilogue stage");
   conv_epilogue<MI, NI>(p, acc, reinterpret_cast<float *>(lds), m0, n0, wm, wn, half, l31);
@@ -196,20 +183,6 @@ __global__ __launch_bounds__(64 * WM * WN, BM * BN > 128 * 128 ? 2 : 3) void con
 
 int launch_conv_bf16x6(const ConvParams &p, int bm, int bn, hipStream_t s) {
   dim3 grid((p.M + bm - 1) / bm, p.n_p / bn, p.splits);
-#ifdef DT_TOOLS   // ablation instantiations (wrong results by design) exist only in a tools build (build.py --tools)
-  if (p.ablate && bm == 128 && bn == 128) {     // timing experiments (tools/ablate.py)
-    switch (p.ablate) {
-      case 1: conv_gemm_bf16x6_kernel<128, 128, 1><<<grid, 256, 0, s>>>(p); break;
-      case 2: conv_gemm_bf16x6_kernel<128, 128, 2><<<grid, 256, 0, s>>>(p); break;
-      case 3: conv_gemm_bf16x6_kernel<128, 128, 3><<<grid, 256, 0, s>>>(p); break;
-      case 4: conv_gemm_bf16x6_kernel<128, 128, 4><<<grid, 256, 0, s>>>(p); break;
-      case 5: conv_gemm_bf16x6_kernel<128, 128, 5><<<grid, 256, 0, s>>>(p); break;
-      default: return DT_E_ARG;
-    }
-    DT_LAUNCH_CHECK();
-    return DT_OK;
-  }
-#endif
   if (bm == 128 && bn == 128) conv_gemm_bf16x6_kernel<128, 128><<<grid, 256, 0, s>>>(p);
   else if (bm == 128) conv_gemm_bf16x6_kernel<128, 64><<<grid, 256, 0, s>>>(p);
   else if (bn == 128) conv_gemm_bf16x6_kernel<64, 128><<<grid, 256, 0, s>>>(p);

@@ -37,7 +37,7 @@ constexpr int epilogue_stage_floats() { return WM * 32 * (BN + 4); }
 // Epilogue of every convolution kernel, staged through LDS.
 //
 // The accumulator layout (lane = column, register = row) makes a direct epilogue store 4 bytes per lane, and the
-// side inputs (residual, time bias) load the same way: measured per-workgroup timelines (tools/block_timeline.py)
+// side inputs (residual, time bias) load the same way: measured per-workgroup timelines
 // put such an epilogue at 14 us for a 128 x 128 tile on an idle chip and 28-35 us with a residual or the fused pool
 // (one exposed memory latency per accumulator register).  Here a 32-row accumulator tile of each wave row goes
 // through LDS once ([WM * 32][BN + 4] floats, conflict-free both ways) and comes back as float4 per lane with a whole

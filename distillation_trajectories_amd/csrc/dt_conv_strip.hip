@@ -29,15 +29,13 @@ namespace dt {
 
 extern __shared__ __attribute__((aligned(16))) __bf16 strip_lds[];
 
-// ABL != 0: timing experiments (wrong results): 1 no per-tap barrier, 2 no weight staging, 3 no MFMA,
-// 4 no fragment reads after the first step, 5 no strip re-staging
 // KC = 16-channel chunks staged and multiplied per step (1 or 2): KC = 2 halves the barriers and doubles the
 // MFMAs between them at twice the LDS footprint and staging registers (2 waves/SIMD instead of 3).
 // WK = waves that share one output tile and split the step's KC chunks between them (1, 2 or 4): small layers need
 // small workgroup tiles to fill the chip, and a 64 x 64 tile cut 2 x 2 leaves each wave 32 x 32 (6 fragment reads per
 // 6 MFMAs, ~100 TF/s).  With WK = 4 every wave keeps a 64 x 64 accumulator (12 reads per 24 MFMAs) over a quarter of
 // the channels and the four partial tiles are summed in wave order in the staged epilogue -- split-K without slabs.
-template <int BM, int BN, int ABL = 0, int KC = 1, int WK = 1>
+template <int BM, int BN, int KC = 1, int WK = 1>
 __global__ __launch_bounds__(256, KC == 1 ? 3 : 2) void conv_strip_bf16x6_kernel(const ConvParams p) {
   // four waves: 2 x 2 over the tile, or 4 x 1 for the 256 x 64 tile (a 64 x 64 wave tile -- 12 fragment reads per 24
   // MFMAs, like the 128 x 128 tile -- for layers with 64 output channels, where 128 x 64 leaves each wave 64 x 32),
@@ -182,10 +180,9 @@ __global__ __launch_bounds__(256, KC == 1 ? 3 : 2) void conv_strip_bf16x6_kernel
     else if (adv == ADV_SKIP0) wrun = wbase2;
     else if (adv == ADV_SKIP) wrun += group_stride;
     if (b_thread) {
-      const __bf16 *wt = ABL == 6 ? wbase : wrun;                  // ABL 6: every tile re-reads the first one (cache-hot)
 #pragma unroll
       for (int i = 0; i < NB; ++i)                                 // tile i = (chunk, plane): consecutive chunks of one tap are 3 planes apart
-        rb[i] = *reinterpret_cast<const u32x4 *>(wt + (SB * i) * w_plane);
+        rb[i] = *reinterpret_cast<const u32x4 *>(wrun + (SB * i) * w_plane);
     }
   };
   auto write_b = [&](int stage) __attribute__((always_inline)) {
@@ -201,7 +198,7 @@ __global__ __launch_bounds__(256, KC == 1 ? 3 : 2) void conv_strip_bf16x6_kernel
   // and costs a barrier per tap.  The packed tile in global memory IS the LDS image (half-swap swizzle included), so a lane's
   // B fragment is one 16-byte load; the fragments of step s + 1 are requested before the MFMAs of step s, and the only
   // barriers left are the two around a strip restage.
-  constexpr bool DB = WK > 1 && ABL == 0;
+  constexpr bool DB = WK > 1;
   bf16x8 fbn[KW][NI][3];
   auto load_bd = [&](int adv) __attribute__((always_inline)) {
     if (adv == ADV_TAP) wrun += tap_stride;
@@ -218,7 +215,6 @@ __global__ __launch_bounds__(256, KC == 1 ? 3 : 2) void conv_strip_bf16x6_kernel
           fbn[kw][ni][pl] = *reinterpret_cast<const bf16x8 *>(wt + ((wk * KW + kw) * 3 + pl) * w_plane + b_frag[ni]);
   };
 
-  const long long tl0 = p.ablate == 8 ? wall_clock64() : 0;      // timeline diagnostic (tools/block_timeline.py)
   // ---- prologue: strip of chunk 0, weights of step 0, the zero row
   load_strip(0);
   if (DB) load_bd(ADV_NONE); else load_b(ADV_NONE);
@@ -227,30 +223,15 @@ __global__ __launch_bounds__(256, KC == 1 ? 3 : 2) void conv_strip_bf16x6_kernel
   if (!DB) write_b(0);
   __syncthreads();
 
-  // ABL == 9 (diagnostic build, tools/tap_phases.py): s_memtime stamps split every step into
-  //   [0] fragment reads + MFMA issue, [1] wait for the next tap's weight loads, [2] their LDS writes, [3] barrier wait
-  // summed per wave in scalar registers; the real kernel executes none of this.
-  unsigned long long ph[4] = {0, 0, 0, 0}, ts = 0;
-  auto stamp = [&](int seg) __attribute__((always_inline)) {
-    if (ABL != 9) return;
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    if (seg >= 0) ph[seg] += t - ts;
-    ts = t;
-  };
-  stamp(-1);
   // One step = one tap of one (KC-chunk) group.  TT is the tap as a compile-time constant: the nine taps of a main
   // chunk are unrolled, so shifts, mask bits and the whole walk bookkeeping fold away and only the chunk loop is
   // left as scalar control.
-  const long long tl_pro = p.ablate == 8 ? wall_clock64() : 0;
   int step = 0;
   bool stage_next_strip = true;            // false: the next step is a skip step that takes its activations straight from global memory
   auto do_step = [&](auto TT, int ch, bool first_tap, bool last_tap, bool next_chunk, int adv) __attribute__((always_inline)) {
     constexpr int tt = decltype(TT)::value;
     const bool more = !last_tap || next_chunk;
-    if (first_tap && next_chunk && stage_next_strip && ABL != 5) load_strip(ch + 1);   // lands while this chunk's taps run
+    if (first_tap && next_chunk && stage_next_strip) load_strip(ch + 1);   // lands while this chunk's taps run
     bf16x8 fbc[KW][NI][3];                                         // DB: this step's weight fragments (requested during the previous step)
     if (DB) {
 #pragma unroll
@@ -260,7 +241,7 @@ __global__ __launch_bounds__(256, KC == 1 ? 3 : 2) void conv_strip_bf16x6_kernel
 #pragma unroll
           for (int pl = 0; pl < 3; ++pl) fbc[kw][ni][pl] = fbn[kw][ni][pl];
       if (more) load_bd(adv);
-    } else if (more && ABL != 2) load_b(adv);
+    } else if (more) load_b(adv);
     {
       int wv = p.W;
       asm volatile("" : "+s"(wv));           // likewise: do not keep nine precomputed shifts in SGPRs
@@ -283,27 +264,21 @@ __global__ __launch_bounds__(256, KC == 1 ? 3 : 2) void conv_strip_bf16x6_kernel
         const __bf16 *A = As + kk * 3 * PLANE_A;
         const __bf16 *B = Bs + ((step & 1) * KC + kk) * STAGE_B;
         bf16x8 fb[NI][3];
-        const u32x4 fake = {(unsigned)lane * 0x01010101u + (unsigned)a_e[0], 0x3f803f80u, (unsigned)step, 0x3c003c00u};   // ABL == 4 only
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni)
 #pragma unroll
           for (int pl = 0; pl < 3; ++pl)
-            fb[ni][pl] = DB ? fbc[kw][ni][pl]
-                            : ((ABL == 4) ? __builtin_bit_cast(bf16x8, fake) : *reinterpret_cast<const bf16x8 *>(B + pl * PLANE_B + b_frag[ni]));
+            fb[ni][pl] = DB ? fbc[kw][ni][pl] : *reinterpret_cast<const bf16x8 *>(B + pl * PLANE_B + b_frag[ni]);
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi) {
           bf16x8 fa[3];
 #pragma unroll
           for (int pl = 0; pl < 3; ++pl)
-            fa[pl] = (ABL == 4) ? __builtin_bit_cast(bf16x8, fake) : *reinterpret_cast<const bf16x8 *>(A + pl * PLANE_A + a_e[mi]);
+            fa[pl] = *reinterpret_cast<const bf16x8 *>(A + pl * PLANE_A + a_e[mi]);
 #pragma unroll
           for (int ni = 0; ni < NI; ++ni) {
             // smallest terms first so their sum is formed before it meets the large partial sums
             f32x16 c = acc[mi][ni];
-            if (ABL == 3) {              // keep the fragments live, skip the matrix work
-              asm volatile("" :: "v"(fa[0]), "v"(fa[1]), "v"(fa[2]), "v"(fb[ni][0]), "v"(fb[ni][1]), "v"(fb[ni][2]));
-              continue;
-            }
             c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[2], fb[ni][0], c, 0, 0, 0);
             c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[ni][1], c, 0, 0, 0);
             c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[ni][2], c, 0, 0, 0);
@@ -315,17 +290,13 @@ __global__ __launch_bounds__(256, KC == 1 ? 3 : 2) void conv_strip_bf16x6_kernel
         }
       }
     }
-    stamp(0);
-    if (ABL == 9) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stamp(1); }
-    if (!DB && more && ABL != 2) write_b((step + 1) & 1);
-    stamp(2);
-    const bool restage = last_tap && next_chunk && stage_next_strip && ABL != 5;
+    if (!DB && more) write_b((step + 1) & 1);
+    const bool restage = last_tap && next_chunk && stage_next_strip;
     if (restage) {
       __syncthreads();                                             // every wave is done with this chunk's strip
       write_strip();
     }
-    if (DB ? restage : (ABL != 1 || last_tap)) __syncthreads();
-    stamp(3);
+    if (!DB || restage) __syncthreads();
     ++step;
   };
 
@@ -335,7 +306,7 @@ __global__ __launch_bounds__(256, KC == 1 ? 3 : 2) void conv_strip_bf16x6_kernel
   // of step s + 1 issued only one (single-tap) step ahead: 25-40 us per layer for 2-4 GFLOP.  Here the loads of step s + 2 are
   // issued when step s has consumed its registers (two register sets, the strip staging registers being idle), the weight
   // tile keeps its double buffer and a step has one barrier.
-  constexpr bool DIRECT = MI * KW <= 2 && KC >= 2 && ABL == 0;   // (K = 16 steps: 3 waves per SIMD leave no registers for the two sets)
+  constexpr bool DIRECT = MI * KW <= 2 && KC >= 2;   // (K = 16 steps: 3 waves per SIMD leave no registers for the two sets)
   f32x4 ga0[KW][MI][2], ga1[KW][MI][2];
   const int n_skip = p.in2 ? (CC2 + KC - 1) / KC : 0;
   auto load_a = [&](f32x4 (&g)[KW][MI][2], int s2) __attribute__((always_inline)) {
@@ -407,7 +378,7 @@ __global__ __launch_bounds__(256, KC == 1 ? 3 : 2) void conv_strip_bf16x6_kernel
   // (Only for grids of at most two workgroups per CU: with three resident ones two would share a priority -- measured
   // 11 % slower on enc1.conv2's 1024 workgroups -- and larger grids refill CUs at arbitrary times anyway.)
   const int prio_grp = ((blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z)) >> 8) & 1;
-  const bool use_prio = p.ablate != 7 && gridDim.x * gridDim.y * gridDim.z <= 512;
+  const bool use_prio = gridDim.x * gridDim.y * gridDim.z <= 512;
   for (int ch = 0; ch < n_main; ++ch) {                            // 3x3 walk: nine unrolled taps per chunk group
     if (use_prio) {
       if ((ch ^ prio_grp) & 1) __builtin_amdgcn_s_setprio(1);
@@ -483,21 +454,7 @@ __global__ __launch_bounds__(256, KC == 1 ? 3 : 2) void conv_strip_bf16x6_kernel
     for (int ch = n_main; ch < n_chunks; ++ch)                     // fused 1x1 skip walk through the strip: centre tap only
       do_step(std::integral_constant<int, 4>{}, ch, true, true, ch + 1 < n_chunks, ADV_SKIP);
   }
-  const long long tl1 = p.ablate == 8 ? wall_clock64() : 0;
   conv_epilogue<MI, NI, WM, WK>(p, acc, reinterpret_cast<float *>(strip_lds), m0, n0, wm, wn, half, l31, wk);
-  if (ABL == 9) {                          // per-wave phase sums (cycles) + step count into the unused split-K slab
-    if (lane == 0) {
-      unsigned long long *rec = reinterpret_cast<unsigned long long *>(p.slab) + 8 * (4 * (blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z)) + wave);
-      rec[0] = ph[0]; rec[1] = ph[1]; rec[2] = ph[2]; rec[3] = ph[3]; rec[4] = (unsigned long long)step;
-    }
-  }
-  if (p.ablate == 8 && p.splits == 1) {   // (start, prologue end, loop end, end) per workgroup into the unused split-K slab
-    __syncthreads();
-    if (tid == 0) {
-      long long *rec = reinterpret_cast<long long *>(p.slab) + 4 * (blockIdx.x + gridDim.x * blockIdx.y);
-      rec[0] = tl0; rec[1] = tl_pro; rec[2] = tl1; rec[3] = wall_clock64();
-    }
-  }
 }
 
 // p passed conv_admissible (dt_conv.hip): a full 3x3 walk whose tile, chunk groups and LDS footprint the kind supports
@@ -517,48 +474,32 @@ int launch_conv_strip(const ConvParams &p_in, hipStream_t s) {
       if (need > lds) lds = need;
     }
   }
-#ifdef DT_TOOLS   // ablation instantiations (wrong results by design) exist only in a tools build (build.py --tools)
-  if (p.ablate && p.ablate != 7 && p.ablate != 8 && bm == 128 && bn == 128) {     // timing experiments (tools/ablate.py)
-    switch (p.ablate) {
-      case 1: conv_strip_bf16x6_kernel<128, 128, 1><<<grid, 256, lds, s>>>(p); break;
-      case 2: conv_strip_bf16x6_kernel<128, 128, 2><<<grid, 256, lds, s>>>(p); break;
-      case 3: conv_strip_bf16x6_kernel<128, 128, 3><<<grid, 256, lds, s>>>(p); break;
-      case 4: conv_strip_bf16x6_kernel<128, 128, 4><<<grid, 256, lds, s>>>(p); break;
-      case 5: conv_strip_bf16x6_kernel<128, 128, 5><<<grid, 256, lds, s>>>(p); break;
-      case 6: conv_strip_bf16x6_kernel<128, 128, 6><<<grid, 256, lds, s>>>(p); break;
-      case 9: conv_strip_bf16x6_kernel<128, 128, 9><<<grid, 256, lds, s>>>(p); break;
-      default: return DT_E_ARG;
-    }
-    DT_LAUNCH_CHECK();
-    return DT_OK;
-  }
-#endif
   if (kind != KIND_STRIP) {
     static std::once_flag attr_once;   // 128x128 needs 80 KB of dynamic LDS; launches come from several host threads
     static int attr_status = DT_OK;
     std::call_once(attr_once, [] {
-      const void *fns[8] = {reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<64, 128, 0, 2, 2>),
-                            reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<64, 64, 0, 4, 4>),
-                            reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<128, 64, 0, 2, 2>),
-                            reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<256, 64, 0, 2>),
-                            reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<128, 128, 0, 2>),
-                            reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<128, 64, 0, 2>),
-                            reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<64, 128, 0, 2>),
-                            reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<64, 64, 0, 2>)};
+      const void *fns[8] = {reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<64, 128, 2, 2>),
+                            reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<64, 64, 4, 4>),
+                            reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<128, 64, 2, 2>),
+                            reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<256, 64, 2>),
+                            reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<128, 128, 2>),
+                            reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<128, 64, 2>),
+                            reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<64, 128, 2>),
+                            reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<64, 64, 2>)};
       for (const void *f : fns) {
         const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 98304);
         if (e != hipSuccess) attr_status = (int)e;
       }
     });
     if (attr_status != DT_OK) return attr_status;
-    if (kind == KIND_STRIPK && bn == 128) conv_strip_bf16x6_kernel<64, 128, 0, 2, 2><<<grid, 256, lds, s>>>(p);
-    else if (kind == KIND_STRIPK && bm == 64) conv_strip_bf16x6_kernel<64, 64, 0, 4, 4><<<grid, 256, lds, s>>>(p);
-    else if (kind == KIND_STRIPK) conv_strip_bf16x6_kernel<128, 64, 0, 2, 2><<<grid, 256, lds, s>>>(p);
-    else if (bm == 256) conv_strip_bf16x6_kernel<256, 64, 0, 2><<<grid, 256, lds, s>>>(p);
-    else if (bm == 128 && bn == 128) conv_strip_bf16x6_kernel<128, 128, 0, 2><<<grid, 256, lds, s>>>(p);
-    else if (bm == 128) conv_strip_bf16x6_kernel<128, 64, 0, 2><<<grid, 256, lds, s>>>(p);
-    else if (bn == 128) conv_strip_bf16x6_kernel<64, 128, 0, 2><<<grid, 256, lds, s>>>(p);
-    else conv_strip_bf16x6_kernel<64, 64, 0, 2><<<grid, 256, lds, s>>>(p);
+    if (kind == KIND_STRIPK && bn == 128) conv_strip_bf16x6_kernel<64, 128, 2, 2><<<grid, 256, lds, s>>>(p);
+    else if (kind == KIND_STRIPK && bm == 64) conv_strip_bf16x6_kernel<64, 64, 4, 4><<<grid, 256, lds, s>>>(p);
+    else if (kind == KIND_STRIPK) conv_strip_bf16x6_kernel<128, 64, 2, 2><<<grid, 256, lds, s>>>(p);
+    else if (bm == 256) conv_strip_bf16x6_kernel<256, 64, 2><<<grid, 256, lds, s>>>(p);
+    else if (bm == 128 && bn == 128) conv_strip_bf16x6_kernel<128, 128, 2><<<grid, 256, lds, s>>>(p);
+    else if (bm == 128) conv_strip_bf16x6_kernel<128, 64, 2><<<grid, 256, lds, s>>>(p);
+    else if (bn == 128) conv_strip_bf16x6_kernel<64, 128, 2><<<grid, 256, lds, s>>>(p);
+    else conv_strip_bf16x6_kernel<64, 64, 2><<<grid, 256, lds, s>>>(p);
     DT_LAUNCH_CHECK();
     return DT_OK;
   }

@@ -58,7 +58,6 @@ struct FusedArgs {
   float coef[kFusedMaxSteps][3];
   unsigned long long noise_mask;       // bit i: step i adds noise
   double flops_per_row;                // profiler only
-  unsigned long long *trace;           // tools build: s_memtime stamps of workgroup 0's first step, one per layer (else nullptr)
   FusedLds lds;
   float w_scalar;
   int n_ops, mode, rule, n_steps;

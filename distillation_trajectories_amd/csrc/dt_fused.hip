@@ -28,10 +28,7 @@
 // waves: there the taps of a pair are split across waves (FusedOp::ks) and the partial tiles meet in LDS.
 //
 // The layer sequence is a small table (FusedOp) built on the host; LDS buffer placement is in fused_lds() below.
-#include <cstdio>
-#include <cstdlib>
 #include <mutex>
-#include <vector>
 
 #include "dt_conv_epilogue.h"
 #include "dt_update_math.h"
@@ -470,9 +467,6 @@ __global__ __launch_bounds__(kThreads, 4) void unet_fused_kernel(const FusedArgs
       zv[r] = (a.mode == FUSED_LOOP && noise && i < n_img * E) ? a.z[(size_t)((long long)zrow[r] + a.z_shift[st]) * E + e] : 0.f;
     }
     if (!dead) {
-#ifdef DT_TOOLS
-      if (a.trace && tid == 0 && st == (a.n_steps > 1 ? 1 : 0)) a.trace[blockIdx.x * 32] = __builtin_readcyclecounter();
-#endif
       for (int li = 0; li < a.n_ops; ++li) {
         const FusedOp &op = ops[li];
         switch (op.kind) {
@@ -485,9 +479,6 @@ __global__ __launch_bounds__(kThreads, 4) void unet_fused_kernel(const FusedArgs
           default: fused_head(op, L, a.c0p, G, tid); break;
         }
         __syncthreads();
-#ifdef DT_TOOLS
-        if (a.trace && tid == 0 && st == (a.n_steps > 1 ? 1 : 0)) a.trace[blockIdx.x * 32 + li + 1] = __builtin_readcyclecounter();
-#endif
       }
     }
     if (a.mode == FUSED_FORWARD) {
@@ -522,9 +513,6 @@ __global__ __launch_bounds__(kThreads, 4) void unet_fused_kernel(const FusedArgs
     }
     if (st + 1 < n_iter) load_tb(st + 1);           // (every layer of this step is behind a barrier: the rows are free)
     __syncthreads();
-#ifdef DT_TOOLS
-    if (a.trace && tid == 0 && st == (a.n_steps > 1 ? 1 : 0)) a.trace[blockIdx.x * 32 + 31] = __builtin_readcyclecounter();
-#endif
   }
 }
 
@@ -723,37 +711,6 @@ int launch_unet_fused(const FusedArgs &a, hipStream_t s) {
   }
   const int steps = a.mode == FUSED_FORWARD ? 1 : a.n_steps;
   ProfileScope prof(KC_FUSED, a.flops_per_row * Bt * steps, 4.0 * a.B * a.C * 256 * (steps + 1.0), s);
-#ifdef DT_TOOLS
-  if (getenv("DT_FUSED_TRACE")) {     // per-layer cycle stamps of the second step (tools/fused_check.py), averaged over the workgroups
-    FusedArgs t = a;
-    unsigned long long *dev = nullptr;
-    DT_HIP_TRY(hipMalloc((void **)&dev, (size_t)grid * 32 * sizeof(unsigned long long)));
-    DT_HIP_TRY(hipMemsetAsync(dev, 0, (size_t)grid * 32 * sizeof(unsigned long long), s));
-    t.trace = dev;
-    unet_fused_kernel<<<grid, kThreads, lds, s>>>(t, t.ops);
-    DT_HIP_TRY(hipStreamSynchronize(s));
-    std::vector<unsigned long long> h((size_t)grid * 32);
-    DT_HIP_TRY(hipMemcpy(h.data(), dev, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    (void)hipFree(dev);
-    FusedOp ops[kFusedMaxOps];
-    DT_HIP_TRY(hipMemcpy(ops, a.ops, sizeof(FusedOp) * a.n_ops, hipMemcpyDeviceToHost));
-    fprintf(stderr, "[dt_fused] grid %d, cycles per layer of one step (mean over workgroups):\n", grid);
-    double total = 0;
-    for (int li = 0; li <= a.n_ops; ++li) {
-      double sum = 0; int n = 0;
-      for (int g = 0; g < grid; ++g) {
-        const unsigned long long t0 = h[(size_t)g * 32 + li], t1 = h[(size_t)g * 32 + (li == a.n_ops ? 31 : li + 1)];
-        if (t0 && t1 > t0) { sum += (double)(t1 - t0); ++n; }
-      }
-      if (!n) continue;
-      total += sum / n;
-      if (li < a.n_ops) fprintf(stderr, "  op %2d kind %d wsh %d pb %d ks %d kc %d ot %d emode %d: %9.0f\n", li, ops[li].kind, ops[li].wsh, ops[li].pb, ops[li].ks, ops[li].kc, ops[li].ot, ops[li].emode, sum / n);
-      else fprintf(stderr, "  update / store: %9.0f\n", sum / n);
-    }
-    fprintf(stderr, "  total %9.0f cycles\n", total);
-    return DT_OK;
-  }
-#endif
   unet_fused_kernel<<<grid, kThreads, lds, s>>>(a, a.ops);
   DT_LAUNCH_CHECK();
   return DT_OK;

@@ -149,7 +149,6 @@ struct ConvParams {
   // layers with an odd chunk count (cin_p = 48, 80, 112, 208, 240: size factors 0.3, 0.4, 0.6, 0.8, 0.9): the walk is
   // ceil(chunks / step) steps, the activation loads of a chunk >= cin_p / 16 are replaced by zeros
   int ccw, ccw2;
-  int ablate;          // timing experiments only (wrong results): 1 no barrier, 2 no LDS reads, 3 no MFMA, 4 no staging
 };
 
 int launch_conv(const ConvParams &p, hipStream_t s);

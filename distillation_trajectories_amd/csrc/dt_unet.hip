@@ -795,9 +795,6 @@ int dt_unet_time_conv(const dt_unet *h, int batch_total, int H, int W, int block
   const ResolvedForward f = resolve_forward(h, batch_total, H, W, req.imgs, req.single, &req);
   ConvParams p = bind_conv(h, f, block, slot, f.c[block][slot], in, ws, pl, h->slab, batch_total);
   *flops = 2.0 * p.M * (double)p.cout_real * ((double)p.cin_real * p.ksize * p.ksize + (p.in2 ? p.cin2_real : 0));
-#ifdef DT_TOOLS
-  if (const char *ab = getenv("DT_ABLATE")) p.ablate = atoi(ab);   // timing experiments only (tools build: build.py --tools)
-#endif
   hipEvent_t e0, e1;
   DT_HIP_TRY(hipEventCreate(&e0));
   DT_HIP_TRY(hipEventCreate(&e1));
