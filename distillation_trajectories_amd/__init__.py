@@ -24,6 +24,8 @@ _ALIASES = {
     "analysis.metrics.time_dependent": "analysis.metrics.time_dependent",
     "analysis.metrics.fid_score": "analysis.metrics.fid_score",
     "analysis.noise_prediction.noise_analysis": "analysis.noise_prediction.noise_analysis",
+    "analysis.dimensionality.dimensionality_reduction": "analysis.dimensionality.dimensionality_reduction",
+    "analysis.dimensionality.latent_space": "analysis.dimensionality.latent_space",
     "evaluation.metrics": "evaluation.metrics",
 }
 

@@ -97,6 +97,17 @@ INCEPTION_SIGNATURES = {
 }
 
 
+# name -> (restype, argtypes) of every symbol include/dt_hip_pca.h declares (the dimensionality analysis)
+PCA_SIGNATURES = {
+    "dt_pca_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dt_pca_fit": (c_int, [c_void_p, c_int, c_longlong, c_longlong, c_void_p, c_int, c_longlong, c_longlong, c_int, c_int,
+                           c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                           c_void_p, c_void_p]),
+    "dt_pca_project": (c_int, [c_void_p, c_int, c_longlong, c_longlong, c_void_p, c_int, c_longlong, c_longlong, c_int,
+                               c_int, c_int, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p]),
+}
+
+
 def load(path=None):
     """Load (once) and return the library with argtypes set.  Raises HipLibraryError if absent."""
     global _LIB
@@ -112,7 +123,7 @@ def load(path=None):
         lib = ctypes.CDLL(path)
     except OSError as e:
         raise HipLibraryError(f"cannot load {path}: {e}. There is no CPU fallback.") from e
-    for name, (res, args) in {**SIGNATURES, **NOISE_SIGNATURES, **INCEPTION_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **NOISE_SIGNATURES, **INCEPTION_SIGNATURES, **PCA_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -572,6 +572,138 @@ def device_sample_mean(traj):
     return out
 
 
+# ---------------------------------------------------------------------- PCA (include/dt_hip_pca.h)
+PCA_MAX_K = 16
+
+
+def _pca_rows(t, name):
+    """[n, P, E] view of a step-major tensor (a 2-D [n, E] tensor is one problem); shape errors are ValueErrors."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name} must be a torch tensor, got {type(t).__name__}")
+    if t.dim() == 2:
+        t = t.unsqueeze(1)
+    if t.dim() != 3:
+        raise ValueError(f"{name} must be [n, E] or step-major [n, P, E], got shape {tuple(t.shape)}")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{name} must be float32, got {t.dtype}")
+    return t
+
+
+def _pca_pad(t, E4):
+    """t [n, P, E] as the kernel reads it: rows 16-byte aligned, E zero-padded to E4 (a PCA is blind to zero columns)."""
+    E = t.shape[-1]
+    if E != E4:
+        return torch.nn.functional.pad(t, (0, E4 - E)).contiguous()
+    if t.stride(-1) != 1 or t.data_ptr() % 16 or t.stride(0) % 4 or t.stride(1) % 4:
+        return t.contiguous()
+    return t
+
+
+def _pca_check(a, b, k):
+    a = _pca_rows(a, "a")
+    b = None if b is None else _pca_rows(b, "b")
+    n_a, P, E = a.shape
+    n_b = 0 if b is None else b.shape[0]
+    if b is not None and tuple(b.shape[1:]) != (P, E):
+        raise ValueError(f"b {tuple(b.shape)} does not match a {tuple(a.shape)}: every row needs the same length and the "
+                         "same number of problems")
+    n = n_a + n_b
+    if n < 2 or n_a < 1:
+        raise ValueError(f"a PCA needs n >= 2 rows (a first), got n_a={n_a}, n_b={n_b}")
+    if not 1 <= P <= 65535 or E < 1:
+        raise ValueError(f"unsupported shape: P={P}, E={E}")
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= min(PCA_MAX_K, n - 1, E):
+        raise ValueError(f"n_components={k!r} must be an int in [1, min({PCA_MAX_K}, n - 1, E)] = [1, "
+                         f"{min(PCA_MAX_K, n - 1, E)}]")
+    return a, b, int(k)
+
+
+def device_pca(a, k, b=None, events=None):
+    """Exact PCA (sklearn ``PCA(k, svd_solver="full")`` on the float64 copy) of every problem p of the step-major device
+    tensors a [n_a, P, E] and b [n_b, P, E] (rows a[:, p] then b[:, p]; a 2-D [n, E] tensor is one problem), in place
+    when the rows are 16-byte aligned and E % 4 == 0.  Returns device tensors {mean [P, E] fp32, components [P, k, E] fp32,
+    scores [P, n, k] fp32, singular_values / explained_variance / explained_variance_ratio [P, k] fp64, status [P] int32}
+    (status: 0 ok, 1 non-finite input, 2 zero total variance).  ``events``: None or 4 torch.cuda.Event(enable_timing=True)
+    recorded at the stage boundaries (dt_pca_fit)."""
+    a, b, k = _pca_check(a, b, k)
+    _require_cuda(a, "a")
+    if b is not None:
+        _require_cuda(b, "b")
+    lib = _hip.load()
+    n_a, P, E = a.shape
+    n_b = 0 if b is None else b.shape[0]
+    n, E4 = n_a + n_b, E + (-E % 4)
+    a = _pca_pad(a, E4)
+    b = None if b is None else _pca_pad(b, E4)
+    dev = a.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    f64 = dict(dtype=torch.float64, device=dev)
+    out = {"mean": torch.empty(P, E4, **f32), "components": torch.empty(P, k, E4, **f32),
+           "scores": torch.empty(P, n, k, **f32), "singular_values": torch.empty(P, k, **f64),
+           "explained_variance": torch.empty(P, k, **f64), "explained_variance_ratio": torch.empty(P, k, **f64),
+           "status": torch.empty(P, dtype=torch.int32, device=dev)}
+    ws_bytes = lib.dt_pca_workspace_bytes(P, n, E4, k)
+    if ws_bytes == 0:
+        raise ValueError(f"dt_pca_workspace_bytes rejects P={P}, n={n}, E={E4}, k={k}")
+    ev = None
+    if events is not None:
+        if len(events) != 4:
+            raise ValueError("events must be 4 torch.cuda.Event")
+        for e in events:                 # torch creates the HIP event at its first record
+            e.record()
+        ev = (c_void_p * 4)(*[e._as_parameter_.value for e in events])
+    with torch.cuda.device(dev):
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        bs = (0, 0) if b is None else (b.stride(1), b.stride(0))
+        check(lib.dt_pca_fit(ptr(a), n_a, a.stride(1), a.stride(0), ptr(b), n_b, bs[0], bs[1], P, E4, k,
+                             ptr(out["mean"]), ptr(out["components"]), ptr(out["scores"]), ptr(out["singular_values"]),
+                             ptr(out["explained_variance"]), ptr(out["explained_variance_ratio"]), ptr(out["status"]),
+                             ptr(ws), ws_bytes, ev, stream_ptr()), "dt_pca_fit")
+    if E4 != E:
+        out["mean"], out["components"] = out["mean"][:, :E], out["components"][:, :, :E]
+    return out
+
+
+def device_pca_project(a, mean, components, b=None):
+    """fp32 scores [P, n, k] = (row - mean) . components^T (fp64 sums, dt_pca_project) for the rows of a [n_a, P, E] and
+    b [n_b, P, E] (as in ``device_pca``); mean [E] / components [k, E] are one basis for every problem, [P, E] /
+    [P, k, E] one per problem."""
+    a = _pca_rows(a, "a")
+    b = None if b is None else _pca_rows(b, "b")
+    n_a, P, E = a.shape
+    if b is not None and tuple(b.shape[1:]) != (P, E):
+        raise ValueError(f"b {tuple(b.shape)} does not match a {tuple(a.shape)}")
+    for t, name in ((mean, "mean"), (components, "components")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise ValueError(f"{name} must be a float32 tensor")
+    shared = components.dim() == 2
+    if shared and (tuple(mean.shape) != (E,) or components.shape[1] != E):
+        raise ValueError(f"mean {tuple(mean.shape)} / components {tuple(components.shape)} do not match E={E}")
+    if not shared and (components.dim() != 3 or tuple(mean.shape) != (P, E) or components.shape[0] != P
+                       or components.shape[2] != E):
+        raise ValueError(f"mean {tuple(mean.shape)} / components {tuple(components.shape)} do not match P={P}, E={E}")
+    k = components.shape[-2]
+    if not 1 <= k <= PCA_MAX_K or not 1 <= P <= 65535:
+        raise ValueError(f"unsupported k={k} or P={P}")
+    for t, name in ((a, "a"), (b, "b"), (mean, "mean"), (components, "components")):
+        if t is not None:
+            _require_cuda(t, name)
+    lib = _hip.load()
+    E4 = E + (-E % 4)
+    a = _pca_pad(a, E4)
+    b = None if b is None else _pca_pad(b, E4)
+    mean = torch.nn.functional.pad(mean, (0, E4 - E)).contiguous()
+    components = torch.nn.functional.pad(components, (0, E4 - E)).contiguous()
+    n_b = 0 if b is None else b.shape[0]
+    out = torch.empty(P, n_a + n_b, k, dtype=torch.float32, device=a.device)
+    bs = (0, 0) if b is None else (b.stride(1), b.stride(0))
+    with torch.cuda.device(a.device):
+        check(lib.dt_pca_project(ptr(a), n_a, a.stride(1), a.stride(0), ptr(b), n_b, bs[0], bs[1], P, E4, k,
+                                 ptr(mean), 0 if shared else E4, ptr(components), 0 if shared else k * E4, ptr(out),
+                                 stream_ptr()), "dt_pca_project")
+    return out
+
+
 def resize_bilinear(images, size):
     """``torch.nn.functional.interpolate(images, size=size, mode='bilinear', align_corners=True)`` for an NCHW fp32 tensor,
     on the device (dt_resize_bilinear); a host tensor is uploaded and the result stays on the device."""
