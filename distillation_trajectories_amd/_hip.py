@@ -108,6 +108,14 @@ PCA_SIGNATURES = {
 }
 
 
+# name -> (restype, argtypes) of every symbol include/dt_hip_fid.h declares (the Fréchet distance of the FID stage)
+FID_SIGNATURES = {
+    "dt_fid_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dt_fid_distance": (c_int, [c_void_p, c_int, c_longlong, c_longlong, c_void_p, c_int, c_longlong, c_longlong, c_int,
+                                c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+}
+
+
 def load(path=None):
     """Load (once) and return the library with argtypes set.  Raises HipLibraryError if absent."""
     global _LIB
@@ -123,7 +131,8 @@ def load(path=None):
         lib = ctypes.CDLL(path)
     except OSError as e:
         raise HipLibraryError(f"cannot load {path}: {e}. There is no CPU fallback.") from e
-    for name, (res, args) in {**SIGNATURES, **NOISE_SIGNATURES, **INCEPTION_SIGNATURES, **PCA_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **NOISE_SIGNATURES, **INCEPTION_SIGNATURES, **PCA_SIGNATURES,
+                              **FID_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

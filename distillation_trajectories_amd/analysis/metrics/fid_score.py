@@ -11,6 +11,11 @@ order.  ``calculate_fid`` is the reference's numpy/scipy formula.
 The InceptionV3 features (reference :19-56) run on the device (``inception.InceptionHandle``, include/dt_hip_inception.h)
 with the user's copy of torchvision's pretrained weights (``weights=`` or ``DT_INCEPTION_WEIGHTS``; never downloaded).
 ``calculate_and_visualize_fid`` is the reference's driver (:96-198) without the figure.
+
+``stats="device"`` (or ``DT_FID_STATS=device``) keeps the features on the device and takes the Fréchet distance there
+too (``calculate_fid_device``, ``engine.device_fid``, include/dt_hip_fid.h): one double comes back.  The default,
+``"host"``, is the reference's numpy/scipy formula on the copied features.  ``fid_sweep`` scores several students against
+one teacher in one batched device call.
 """
 import os
 
@@ -38,6 +43,30 @@ def calculate_fid(features_1, features_2):
     if np.iscomplexobj(covmean):
         covmean = covmean.real
     return ssdiff + np.trace(sigma1 + sigma2 - 2.0 * covmean)
+
+
+def stats_mode(stats=None):
+    """"host" or "device": ``stats`` if given, else ``$DT_FID_STATS``, else "host"."""
+    mode = stats if stats is not None else (os.environ.get("DT_FID_STATS") or "host")
+    if mode not in ("host", "device"):
+        raise ValueError(f"stats (or DT_FID_STATS) must be 'host' or 'device', got {mode!r}")
+    return mode
+
+
+def calculate_fid_device(features_1, features_2):
+    """``calculate_fid`` with the arithmetic on the device, in fp64 (``engine.device_fid``): fp32 features [N, D] that are
+    on the device already, or host tensors / arrays that are uploaded first; returns a Python float.  The same 999.0
+    placeholder below 2 samples.  At most 2048 samples in the smaller set; NaN if a feature is NaN or infinite."""
+    if len(features_1) < 2 or len(features_2) < 2:
+        print("  Warning: Not enough samples for a proper FID calculation.")
+        print(f"  Number of samples in set 1: {len(features_1)}")
+        print(f"  Number of samples in set 2: {len(features_2)}")
+        print("  Returning a placeholder FID score of 999.0")
+        return 999.0
+    sets = [torch.as_tensor(f) for f in (features_1, features_2)]
+    device = next((t.device for t in sets if t.is_cuda), torch.device("cuda"))
+    sets = [t if t.is_cuda else t.to(device) for t in sets]
+    return float(engine.device_fid(sets[0], sets[1])["fid"][0])
 
 
 def posterior_coefficients(config):
@@ -135,9 +164,11 @@ def extract_features(images, model=None, weights=None, device=None, batch_size=6
 
 
 def calculate_and_visualize_fid(teacher_model, student_model, config, output_dir=None, size_factor=None,
-                                fixed_samples=None, weights=None):
+                                fixed_samples=None, weights=None, stats=None):
     """Reference :96-198: FID between teacher and student samples; console lines, ``fid_score_size_{sf}.txt`` and the
-    returned ``{"fid_score": ...}`` as the reference's.  No figure is drawn."""
+    returned ``{"fid_score": ...}`` as the reference's.  No figure is drawn.  ``stats``: "host" (the default, unless
+    ``$DT_FID_STATS`` says otherwise) or "device" (``stats_mode``)."""
+    mode = stats_mode(stats)
     if output_dir is None:
         output_dir = os.path.join(config.analysis_dir, "fid", f"size_{size_factor}")
     os.makedirs(output_dir, exist_ok=True)
@@ -152,11 +183,40 @@ def calculate_and_visualize_fid(teacher_model, student_model, config, output_dir
     student_samples = generate_samples(student_model, config, num_samples, device, fixed_samples=fixed_samples)
     print("  Extracting features using InceptionV3...")
     inception_model = InceptionModel(device, weights)
-    teacher_features = inception_model.get_features(teacher_samples)
-    student_features = inception_model.get_features(student_samples)
+    if mode == "device":
+        teacher_features = extract_features(teacher_samples, inception_model, batch_size=32, in_scale=0.5, in_shift=0.5)
+        student_features = extract_features(student_samples, inception_model, batch_size=32, in_scale=0.5, in_shift=0.5)
+    else:
+        teacher_features = inception_model.get_features(teacher_samples)
+        student_features = inception_model.get_features(student_samples)
     print("  Calculating FID score...")
-    fid_score = calculate_fid(teacher_features, student_features)
+    fid_score = (calculate_fid_device if mode == "device" else calculate_fid)(teacher_features, student_features)
     print(f"  FID score for size factor {size_factor}: {fid_score:.4f}")
     with open(os.path.join(output_dir, f"fid_score_size_{size_factor}.txt"), "w") as f:
         f.write(f"FID Score: {fid_score:.4f}\n")
     return {"fid_score": fid_score}
+
+
+def fid_sweep(teacher_model, student_models, config, num_samples, weights=None, fixed_samples=None):
+    """FID of every student against one teacher: the teacher's samples and features once, each student's samples and
+    features (``generate_samples`` in that order, so the CPU generator is consumed as by one
+    ``calculate_and_visualize_fid`` call for the teacher followed by the students), then one batched ``engine.device_fid``
+    with the teacher's features shared.  Returns numpy ``fid [n_students]`` and ``parts [n_students, 4]`` (float64) and
+    ``status [n_students]``; nothing else leaves the device."""
+    student_models = list(student_models)
+    if not student_models:
+        raise ValueError("fid_sweep needs at least one student model")
+    if num_samples < 2:
+        raise ValueError(f"fid_sweep needs num_samples >= 2, got {num_samples}")
+    device = next(teacher_model.parameters()).device
+    inception_model = InceptionModel(device, weights)
+
+    def features(model):
+        model.eval()
+        samples = generate_samples(model, config, num_samples, device, fixed_samples=fixed_samples)
+        return extract_features(samples, inception_model, batch_size=32, in_scale=0.5, in_shift=0.5)
+
+    teacher = features(teacher_model)
+    students = torch.stack([features(m) for m in student_models])
+    res = engine.device_fid(teacher, students)
+    return {k: v.cpu().numpy() for k, v in res.items()}

@@ -12,11 +12,12 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["dt_conv.hip", "dt_conv_bf16.hip", "dt_conv_strip.hip", "dt_layers.hip", "dt_update.hip", "dt_metrics.hip", "dt_fused.hip", "dt_unet.hip",
-           "dt_inception.hip", "dt_pca.hip"]
-HEADERS = ["dt_internal.h", "dt_conv_epilogue.h", "dt_update_math.h", "dt_fused.h", os.path.join("..", "..", "include", "dt_hip.h"),
+           "dt_inception.hip", "dt_pca.hip", "dt_fid.hip"]
+HEADERS = ["dt_internal.h", "dt_tridiag.h", "dt_conv_epilogue.h", "dt_update_math.h", "dt_fused.h", os.path.join("..", "..", "include", "dt_hip.h"),
            os.path.join("..", "..", "include", "dt_hip_noise.h"),
            os.path.join("..", "..", "include", "dt_hip_inception.h"),
-           os.path.join("..", "..", "include", "dt_hip_pca.h")]
+           os.path.join("..", "..", "include", "dt_hip_pca.h"),
+           os.path.join("..", "..", "include", "dt_hip_fid.h")]
 LIB = os.path.join(HERE, "libdt_hip.so")
 ARCH = "gfx950"
 
@@ -90,6 +91,7 @@ SAN_DRIVER = os.path.join(OBJ_DIR, "dt_host_sanitize")
 NOISE_SAN_DRIVER = os.path.join(OBJ_DIR, "dt_host_sanitize_noise")
 INCEPTION_SAN_DRIVER = os.path.join(OBJ_DIR, "dt_host_sanitize_inception")
 PCA_SAN_DRIVER = os.path.join(OBJ_DIR, "dt_host_sanitize_pca")
+FID_SAN_DRIVER = os.path.join(OBJ_DIR, "dt_host_sanitize_fid")
 
 
 def build_sanitizer_driver(verbose=False, driver="driver.cpp", out=SAN_DRIVER):
@@ -134,6 +136,12 @@ def build_pca_sanitizer_driver(verbose=False):
     return build_sanitizer_driver(verbose, driver="pca_driver.cpp", out=PCA_SAN_DRIVER)
 
 
+def build_fid_sanitizer_driver(verbose=False):
+    """The same instrumented build around tests/host_sanitize/fid_driver.cpp, which walks every entry point of
+    include/dt_hip_fid.h: csrc/_build/dt_host_sanitize_fid (run by tests/test_hip_fid.py)."""
+    return build_sanitizer_driver(verbose, driver="fid_driver.cpp", out=FID_SAN_DRIVER)
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     if "--sanitize" in sys.argv:
@@ -141,3 +149,4 @@ if __name__ == "__main__":
         print(build_noise_sanitizer_driver(verbose=True))
         print(build_inception_sanitizer_driver(verbose=True))
         print(build_pca_sanitizer_driver(verbose=True))
+        print(build_fid_sanitizer_driver(verbose=True))

@@ -19,10 +19,9 @@
 
 #include "../../include/dt_hip_pca.h"
 #include "dt_internal.h"
+#include "dt_tridiag.h"
 
 namespace {
-
-constexpr int kThreads = 256;
 
 struct Rows {
   const float *a, *b;
@@ -57,40 +56,6 @@ struct Layout {
   }
   __host__ __device__ size_t bytes(int P) const { return head + (size_t)P * per * sizeof(double); }
 };
-
-__device__ inline double wave_sum(double s) {
-  for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
-  return s;
-}
-
-// fixed-tree sum over the block; every thread gets the result
-__device__ double block_sum(double s, double *red) {
-  const int t = threadIdx.x;
-  red[t] = s;
-  __syncthreads();
-  for (int h = kThreads / 2; h >= 1; h >>= 1) {
-    if (t < h) red[t] += red[t + h];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
-
-__device__ double block_min(double s, double *red) {
-  const int t = threadIdx.x;
-  red[t] = s;
-  __syncthreads();
-  for (int h = kThreads / 2; h >= 1; h >>= 1) {
-    if (t < h) red[t] = fmin(red[t], red[t + h]);
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
-
-__device__ double block_max(double s, double *red) { return -block_min(-s, red); }
 
 // ---------------------------------------------------------------------------------------------- 1. mean and check
 __global__ __launch_bounds__(kThreads) void pca_mean_kernel(Rows R, int E, double *ws, size_t per, int *flag,
@@ -195,104 +160,8 @@ __global__ __launch_bounds__(kThreads) void pca_status_kernel(int n, int E, int 
   }
 }
 
-// ---------------------------------------------------------------------------------------------- 3. tridiagonalisation
-// Step i (0 <= i <= n-3) works on the trailing block [i+1, n).  G stays exactly symmetric (the rank-2 update forms both
-// products and adds them un-contracted), so row i is read as column i, and row i's columns i+2.. then hold the
-// reflector v (v[i+1] = 1 implied): nothing reads row i of the matrix after step i.
-__global__ __launch_bounds__(kThreads) void pca_reflect_kernel(int n, int E, int k, double *ws, size_t per,
-                                                               const int *st, int i) {
-  __shared__ double red[kThreads];
-  const int p = blockIdx.x;
-  if (st[p]) return;
-  const Layout L(0, n, E, k);
-  double *base = ws + (size_t)p * per;
-  double *row = base + L.G + (size_t)i * n;
-  const double alpha = row[i + 1];
-  double s = 0.0;
-  for (int r = i + 2 + threadIdx.x; r < n; r += kThreads) s += row[r] * row[r];
-  const double xn2 = block_sum(s, red);
-  double tau = 0.0, beta = alpha, scale = 0.0;
-  if (xn2 != 0.0) {
-    beta = -copysign(sqrt(alpha * alpha + xn2), alpha);
-    tau = (beta - alpha) / beta;
-    scale = 1.0 / (alpha - beta);
-  }
-  double *v = base + L.v;
-  for (int r = i + 1 + threadIdx.x; r < n; r += kThreads) {
-    if (r == i + 1) {
-      v[r] = 1.0;
-    } else {
-      const double vr = row[r] * scale;
-      v[r] = vr;
-      row[r] = vr;
-    }
-  }
-  if (threadIdx.x == 0) {
-    base[L.tau + i] = tau;
-    base[L.e + i] = beta;
-  }
-}
-
-// p = tau * A22 v: one wave per row, 4 rows per wave, lanes over the columns then a butterfly
-__global__ __launch_bounds__(kThreads) void pca_matvec_kernel(int n, int E, int k, double *ws, size_t per,
-                                                              const int *st, int i) {
-  const int p = blockIdx.y;
-  if (st[p]) return;
-  const Layout L(0, n, E, k);
-  double *base = ws + (size_t)p * per;
-  const double *A = base + L.G, *v = base + L.v;
-  const double tau = base[L.tau + i];
-  const int w = threadIdx.x / 64, lane = threadIdx.x % 64;
-  for (int rr = 0; rr < 4; ++rr) {
-    const int r = i + 1 + (blockIdx.x * 4 + w) * 4 + rr;
-    if (r >= n) break;
-    const double *Ar = A + (size_t)r * n;
-    double s = 0.0;
-    for (int c = i + 1 + lane; c < n; c += 64) s = fma(Ar[c], v[c], s);
-    s = wave_sum(s);
-    if (lane == 0) base[L.pv + r] = tau * s;
-  }
-}
-
-// A22 -= v w^T + w v^T, w = p - 0.5 tau (p.v) v; 64 x 64 tile per workgroup; p.v is summed by every workgroup in the
-// same order
-__global__ __launch_bounds__(kThreads) void pca_update_kernel(int n, int E, int k, double *ws, size_t per,
-                                                              const int *st, int i, int tiles) {
-#pragma clang fp contract(off)
-  __shared__ double red[kThreads];
-  const int p = blockIdx.y;
-  if (st[p]) return;
-  const Layout L(0, n, E, k);
-  double *base = ws + (size_t)p * per;
-  double *A = base + L.G;
-  const double *v = base + L.v, *pv = base + L.pv;
-  double s = 0.0;
-  for (int r = i + 1 + threadIdx.x; r < n; r += kThreads) s = fma(pv[r], v[r], s);
-  const double alpha2 = -0.5 * base[L.tau + i] * block_sum(s, red);
-  const int tr = blockIdx.x / tiles, tc = blockIdx.x % tiles;
-  for (int q = threadIdx.x; q < 64 * 64; q += kThreads) {
-    const int r = i + 1 + tr * 64 + q / 64, c = i + 1 + tc * 64 + q % 64;
-    if (r < n && c < n) {
-      const double wr = pv[r] + alpha2 * v[r], wc = pv[c] + alpha2 * v[c];
-      const double t1 = v[r] * wc, t2 = wr * v[c];
-      A[(size_t)r * n + c] -= t1 + t2;
-    }
-  }
-}
-
-// number of eigenvalues of the tridiagonal (d, e) below x
-__device__ int sturm_below(const double *d, const double *e, int n, double x, double pivmin) {
-  int cnt = 0;
-  double q = d[0] - x;
-  if (fabs(q) < pivmin) q = -pivmin;
-  cnt += q < 0.0;
-  for (int i = 1; i < n; ++i) {
-    q = d[i] - x - e[i - 1] * e[i - 1] / q;
-    if (fabs(q) < pivmin) q = -pivmin;
-    cnt += q < 0.0;
-  }
-  return cnt;
-}
+// ---------------------------------------------------------------------------------------------- 3. eigen stage
+// The tridiagonalisation kernels and sturm_below are in dt_tridiag.h (shared with dt_fid.hip).
 
 __device__ inline double start_entry(int i, int j) {
   unsigned h = (unsigned)i * 2654435761u ^ ((unsigned)j + 1u) * 40503u;
@@ -617,15 +486,8 @@ extern "C" int dt_pca_fit(const float *a_dev, int n_a, long long a_pstride, long
   pca_status_kernel<<<P, kThreads, 0, s>>>(n, E, k, wd, L.per, flag, st, status_dev);
   DT_LAUNCH_CHECK();
   if (events) DT_HIP_TRY(hipEventRecord((hipEvent_t)events[1], s));
-  for (int i = 0; i + 2 < n; ++i) {
-    const int m = n - 1 - i, tiles = (m + 63) / 64;
-    pca_reflect_kernel<<<P, kThreads, 0, s>>>(n, E, k, wd, L.per, st, i);
-    DT_LAUNCH_CHECK();
-    pca_matvec_kernel<<<dim3((m + 15) / 16, P), kThreads, 0, s>>>(n, E, k, wd, L.per, st, i);
-    DT_LAUNCH_CHECK();
-    pca_update_kernel<<<dim3(tiles * tiles, P), kThreads, 0, s>>>(n, E, k, wd, L.per, st, i, tiles);
-    DT_LAUNCH_CHECK();
-  }
+  const Tri T{wd, L.per, L.G, L.v, L.pv, L.e, L.tau, st, n};
+  if (const int rc = tridiagonalise(T, P, s)) return rc;
   pca_eigen_kernel<<<P, kThreads, 0, s>>>(n, E, k, wd, L.per, st);
   DT_LAUNCH_CHECK();
   if (events) DT_HIP_TRY(hipEventRecord((hipEvent_t)events[2], s));

@@ -704,6 +704,95 @@ def device_pca_project(a, mean, components, b=None):
     return out
 
 
+# ---------------------------------------------------------------------- Fréchet distance (include/dt_hip_fid.h)
+FID_MAX_SIDE = 2048
+FID_MAX_ROWS = 32768
+FID_EVENTS = 5
+
+
+def _fid_set(t, name):
+    """[P, n, D] view of a feature set (a 2-D [n, D] tensor is one set); shape errors are ValueErrors."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name} must be a torch tensor, got {type(t).__name__}")
+    if t.dim() not in (2, 3):
+        raise ValueError(f"{name} must be [n, D] or [P, n, D], got shape {tuple(t.shape)}")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{name} must be float32, got {t.dtype}")
+    return t
+
+
+def _fid_check(a, b):
+    a, b = _fid_set(a, "a"), _fid_set(b, "b")
+    if a.shape[-1] != b.shape[-1]:
+        raise ValueError(f"b {tuple(b.shape)} does not match a {tuple(a.shape)}: both sets need the same feature width")
+    if a.dim() == 3 and b.dim() == 3 and a.shape[0] != b.shape[0]:
+        raise ValueError(f"b {tuple(b.shape)} does not match a {tuple(a.shape)}: the same number of problems, or one "
+                         "2-D set shared by all of them")
+    P = a.shape[0] if a.dim() == 3 else (b.shape[0] if b.dim() == 3 else 1)
+    n_a, n_b, D = a.shape[-2], b.shape[-2], a.shape[-1]
+    if n_a < 2 or n_b < 2:
+        raise ValueError(f"a Fréchet distance needs at least 2 samples per set, got n_a={n_a}, n_b={n_b}")
+    if min(n_a, n_b) > FID_MAX_SIDE or max(n_a, n_b) > FID_MAX_ROWS:
+        raise ValueError(f"n_a={n_a}, n_b={n_b}: the device Fréchet distance takes min(n_a, n_b) <= {FID_MAX_SIDE} (and at "
+                         f"most {FID_MAX_ROWS} per set); with more samples than that in both sets the rank is capped by "
+                         "the feature width and the feature-space formula (calculate_fid on the host) is the right one")
+    if not 1 <= P <= 65535:
+        raise ValueError(f"unsupported number of problems P={P}")
+    if D < 4 or D % 4 or D > (1 << 20):
+        raise ValueError(f"the feature width must be a multiple of 4 in [4, 2^20], got D={D}")
+    return a, b, P
+
+
+def _fid_rows(t):
+    """(tensor, problem stride, row stride) as the kernel reads it: unit column stride, 16-byte aligned rows"""
+    if t.stride(-1) != 1 or t.data_ptr() % 16 or any(s % 4 or s < 0 for s in t.stride()[:-1]):
+        t = t.contiguous()
+    return t, (t.stride(0) if t.dim() == 3 else 0), t.stride(-2)
+
+
+def device_fid(a, b, events=None, workspace=None):
+    """Fréchet distance between the feature sets a and b, fp32 on the device: [n, D], or [P, n, D] for P problems; a 2-D
+    set next to a 3-D one is shared by all P problems (one teacher against P students).  All arithmetic is fp64 on the
+    device (dt_fid_distance): ``fid = |mu_a - mu_b|^2 + tr S_a + tr S_b - 2 tr sqrt(S_a S_b)`` with the last term from the
+    singular values of the centred cross product, never a D x D matrix.  Returns device tensors {fid [P] fp64,
+    parts [P, 4] fp64 = (|mu_a - mu_b|^2, tr S_a, tr S_b, tr sqrt(S_a S_b)), status [P] int32} (status: 0 ok, 1 a NaN or
+    Inf in either set, the five doubles then NaN).  Limits: min(n_a, n_b) <= 2048, D % 4 == 0.  ``events``: None or 5
+    torch.cuda.Event(enable_timing=True) recorded at the stage boundaries (dt_fid_distance).  ``workspace``: None (one is
+    allocated) or a uint8 device tensor of at least ``dt_fid_workspace_bytes`` bytes; its contents do not matter."""
+    a, b, P = _fid_check(a, b)
+    if events is not None and len(events) != FID_EVENTS:
+        raise ValueError(f"events must be {FID_EVENTS} torch.cuda.Event")
+    _require_cuda(a, "a")
+    _require_cuda(b, "b")
+    if a.device != b.device:
+        raise ValueError(f"a is on {a.device}, b on {b.device}")
+    lib = _hip.load()
+    n_a, n_b, D = a.shape[-2], b.shape[-2], a.shape[-1]
+    (a, a_ps, a_rs), (b, b_ps, b_rs) = _fid_rows(a), _fid_rows(b)
+    dev = a.device
+    out = {"fid": torch.empty(P, dtype=torch.float64, device=dev),
+           "parts": torch.empty(P, 4, dtype=torch.float64, device=dev),
+           "status": torch.empty(P, dtype=torch.int32, device=dev)}
+    ws_bytes = lib.dt_fid_workspace_bytes(P, n_a, n_b, D)
+    if ws_bytes == 0:
+        raise ValueError(f"dt_fid_workspace_bytes rejects P={P}, n_a={n_a}, n_b={n_b}, D={D}")
+    with torch.cuda.device(dev):
+        ev = None
+        if events is not None:
+            for e in events:                 # torch creates the HIP event at its first record
+                e.record()
+            ev = (c_void_p * FID_EVENTS)(*[e._as_parameter_.value for e in events])
+        ws = workspace
+        if ws is None:
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        elif ws.dtype != torch.uint8 or ws.device != dev or not ws.is_contiguous() or ws.numel() < ws_bytes:
+            raise ValueError(f"workspace must be a contiguous uint8 tensor of >= {ws_bytes} bytes on {dev}")
+        check(lib.dt_fid_distance(ptr(a), n_a, a_ps, a_rs, ptr(b), n_b, b_ps, b_rs, P, D, ptr(out["fid"]),
+                                  ptr(out["parts"]), ptr(out["status"]), ptr(ws), ws_bytes, ev, stream_ptr()),
+              "dt_fid_distance")
+    return out
+
+
 def resize_bilinear(images, size):
     """``torch.nn.functional.interpolate(images, size=size, mode='bilinear', align_corners=True)`` for an NCHW fp32 tensor,
     on the device (dt_resize_bilinear); a host tensor is uploaded and the result stays on the device."""

@@ -10,7 +10,7 @@ import torch
 from scipy.linalg import sqrtm
 
 from .. import engine
-from ..analysis.metrics.fid_score import InceptionModel, extract_features
+from ..analysis.metrics.fid_score import InceptionModel, calculate_fid_device, extract_features, stats_mode
 from ..analysis.metrics.trajectory_metrics import _metrics_device, _stack_on_device
 
 
@@ -18,12 +18,17 @@ def _as_batch(images):
     return torch.cat(list(images)) if isinstance(images, (list, tuple)) else images
 
 
-def compute_fid(real_images, generated_images, device, batch_size=8, weights=None):
+def compute_fid(real_images, generated_images, device, batch_size=8, weights=None, stats=None):
     """Reference :51-116: FID between two image sets (lists of [1, 3, H, W] tensors, or [N, 3, H, W] tensors), taken
     as given (no (x + 1) / 2), with the reference's arithmetic.  ``weights``: torchvision's Inception3 state dict or
-    its path (default ``$DT_INCEPTION_WEIGHTS``)."""
+    its path (default ``$DT_INCEPTION_WEIGHTS``).  ``stats``: "host" (the default, unless ``$DT_FID_STATS`` says
+    otherwise) or "device": the features stay on the device and the distance is taken there (``calculate_fid_device``)."""
+    mode = stats_mode(stats)
     real, gen = _as_batch(real_images), _as_batch(generated_images)
     inception = InceptionModel(device, weights)
+    if mode == "device":
+        return calculate_fid_device(extract_features(real, inception, batch_size=batch_size),
+                                    extract_features(gen, inception, batch_size=batch_size))
     real_features = extract_features(real, inception, batch_size=batch_size).cpu().numpy()
     gen_features = extract_features(gen, inception, batch_size=batch_size).cpu().numpy()
     mu_real = np.mean(real_features, axis=0)
