@@ -400,48 +400,52 @@ __global__ __launch_bounds__(256, KC == 1 ? 3 : 2) void conv_strip_bf16x6_kernel
     do_step(std::integral_constant<int, 6>{}, ch, false, false, next_chunk, ADV_TAP);
     do_step(std::integral_constant<int, 7>{}, ch, false, false, next_chunk, ADV_TAP);
     do_step(std::integral_constant<int, 8>{}, ch, false, true, next_chunk, ch + 1 < n_main ? ADV_GROUP : ADV_SKIP0);
-    if (ch + 1 == n_main && p.in2) {
-      if constexpr (WK == 1) {
-        conv_midpoint<MI, NI>(p, acc, n0, wn, l31);
-      } else {
-        // BN + ReLU apply to the COMPLETE 3x3 sum: the WK partial tiles meet in LDS (free after the last step's barrier), wave
-        // 0 of each group continues with relu(bn(sum)) and the others with zero, and the skip walk restarts the pipeline
-        constexpr int P = BN + 4, COPY = WM * 32 * P;
-        float *red = reinterpret_cast<float *>(strip_lds);
+    if constexpr (WK == 1) {
+      if (ch + 1 == n_main && p.in2) conv_midpoint<MI, NI>(p, acc, n0, wn, l31);
+    }
+  }
+  if constexpr (WK > 1) {
+    // After the loop, not in its last trip: inside it, what the skip walk's prologue loads (the next weight fragments and the
+    // two activation sets, up to 56 registers) counts as live around the loop's back edge, i.e. through every tap of every
+    // chunk group -- <64,64,4,4> then kept 62 registers in scratch and reloaded them around the ninth tap and the restage.
+    if (p.in2) {
+      // BN + ReLU apply to the COMPLETE 3x3 sum: the WK partial tiles meet in LDS (free after the last step's barrier), wave
+      // 0 of each group continues with relu(bn(sum)) and the others with zero, and the skip walk restarts the pipeline
+      constexpr int P = BN + 4, COPY = WM * 32 * P;
+      float *red = reinterpret_cast<float *>(strip_lds);
 #pragma unroll
-        for (int mi = 0; mi < MI; ++mi) {
-          if (mi || DB) __syncthreads();                             // (DB: the last step ended without a barrier; the strip is still being read)
+      for (int mi = 0; mi < MI; ++mi) {
+        if (mi || DB) __syncthreads();                             // (DB: the last step ended without a barrier; the strip is still being read)
 #pragma unroll
-          for (int ni = 0; ni < NI; ++ni)
+        for (int ni = 0; ni < NI; ++ni)
 #pragma unroll
-            for (int r = 0; r < 16; ++r)
-              red[wk * COPY + (wm * 32 + 4 * half + (r & 3) + 8 * (r >> 2)) * P + wn * (NI * 32) + ni * 32 + l31] = acc[mi][ni][r];
-          __syncthreads();
-#pragma unroll
-          for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const float *src = red + (wm * 32 + 4 * half + (r & 3) + 8 * (r >> 2)) * P + wn * (NI * 32) + ni * 32 + l31;
-              float v = src[0];
-#pragma unroll
-              for (int c = 1; c < WK; ++c) v += src[c * COPY];
-              acc[mi][ni][r] = wk == 0 ? v : 0.f;
-            }
-        }
-        if (wk == 0) conv_midpoint<MI, NI>(p, acc, n0, wn, l31);
+          for (int r = 0; r < 16; ++r)
+            red[wk * COPY + (wm * 32 + 4 * half + (r & 3) + 8 * (r >> 2)) * P + wn * (NI * 32) + ni * 32 + l31] = acc[mi][ni][r];
         __syncthreads();
-        if (DB) load_bd(ADV_SKIP0); else load_b(ADV_SKIP0);
-        if (DIRECT) {
-          load_a(ga0, 0);
-          if (n_skip > 1) load_a(ga1, 1);
-        } else {
-          load_strip(n_main);
-          if (tid < 48 * KC) *reinterpret_cast<u32x4 *>(As + (tid >> 4) * PLANE_A + RZ * 16 + (tid & 15) * 8) = u32x4{0u, 0u, 0u, 0u};
-          write_strip();
-        }
-        if (!DB) write_b(step & 1);
-        __syncthreads();
+#pragma unroll
+        for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const float *src = red + (wm * 32 + 4 * half + (r & 3) + 8 * (r >> 2)) * P + wn * (NI * 32) + ni * 32 + l31;
+            float v = src[0];
+#pragma unroll
+            for (int c = 1; c < WK; ++c) v += src[c * COPY];
+            acc[mi][ni][r] = wk == 0 ? v : 0.f;
+          }
       }
+      if (wk == 0) conv_midpoint<MI, NI>(p, acc, n0, wn, l31);
+      __syncthreads();
+      if (DB) load_bd(ADV_SKIP0); else load_b(ADV_SKIP0);
+      if (DIRECT) {
+        load_a(ga0, 0);
+        if (n_skip > 1) load_a(ga1, 1);
+      } else {
+        load_strip(n_main);
+        if (tid < 48 * KC) *reinterpret_cast<u32x4 *>(As + (tid >> 4) * PLANE_A + RZ * 16 + (tid & 15) * 8) = u32x4{0u, 0u, 0u, 0u};
+        write_strip();
+      }
+      if (!DB) write_b(step & 1);
+      __syncthreads();
     }
   }
   __builtin_amdgcn_s_setprio(0);
@@ -455,6 +459,34 @@ __global__ __launch_bounds__(256, KC == 1 ? 3 : 2) void conv_strip_bf16x6_kernel
       do_step(std::integral_constant<int, 4>{}, ch, true, true, ch + 1 < n_chunks, ADV_SKIP);
   }
   conv_epilogue<MI, NI, WM, WK>(p, acc, reinterpret_cast<float *>(strip_lds), m0, n0, wm, wn, half, l31, wk);
+}
+
+// The K = 32 instantiations take up to 96 KB of dynamic LDS (128x128: 80 KB).  The runtime keeps that attribute per device: it
+// is set on the first such launch on each device, not once per process.
+static int strip_lds_attribute() {
+  constexpr int kMaxDevices = 64;
+  static std::mutex mu;                    // launches come from several host threads
+  static int status[kMaxDevices];          // 0 not set yet, 1 set, otherwise -(hip error)
+  int dev = 0;
+  DT_HIP_TRY(hipGetDevice(&dev));
+  if (dev < 0 || dev >= kMaxDevices) return DT_E_ARG;
+  std::lock_guard<std::mutex> lock(mu);
+  if (status[dev] == 0) {
+    const void *fns[8] = {reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<64, 128, 2, 2>),
+                          reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<64, 64, 4, 4>),
+                          reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<128, 64, 2, 2>),
+                          reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<256, 64, 2>),
+                          reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<128, 128, 2>),
+                          reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<128, 64, 2>),
+                          reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<64, 128, 2>),
+                          reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<64, 64, 2>)};
+    status[dev] = 1;
+    for (const void *f : fns) {
+      const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 98304);
+      if (e != hipSuccess) status[dev] = -(int)e;
+    }
+  }
+  return status[dev] == 1 ? DT_OK : -status[dev];
 }
 
 // p passed conv_admissible (dt_conv.hip): a full 3x3 walk whose tile, chunk groups and LDS footprint the kind supports
@@ -475,23 +507,7 @@ int launch_conv_strip(const ConvParams &p_in, hipStream_t s) {
     }
   }
   if (kind != KIND_STRIP) {
-    static std::once_flag attr_once;   // 128x128 needs 80 KB of dynamic LDS; launches come from several host threads
-    static int attr_status = DT_OK;
-    std::call_once(attr_once, [] {
-      const void *fns[8] = {reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<64, 128, 2, 2>),
-                            reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<64, 64, 4, 4>),
-                            reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<128, 64, 2, 2>),
-                            reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<256, 64, 2>),
-                            reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<128, 128, 2>),
-                            reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<128, 64, 2>),
-                            reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<64, 128, 2>),
-                            reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<64, 64, 2>)};
-      for (const void *f : fns) {
-        const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 98304);
-        if (e != hipSuccess) attr_status = (int)e;
-      }
-    });
-    if (attr_status != DT_OK) return attr_status;
+    if (const int st = strip_lds_attribute()) return st;
     if (kind == KIND_STRIPK && bn == 128) conv_strip_bf16x6_kernel<64, 128, 2, 2><<<grid, 256, lds, s>>>(p);
     else if (kind == KIND_STRIPK && bm == 64) conv_strip_bf16x6_kernel<64, 64, 4, 4><<<grid, 256, lds, s>>>(p);
     else if (kind == KIND_STRIPK) conv_strip_bf16x6_kernel<128, 64, 2, 2><<<grid, 256, lds, s>>>(p);

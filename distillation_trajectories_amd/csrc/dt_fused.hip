@@ -690,13 +690,21 @@ double fused_flops_per_row(int C, int c0, int c1) {
 }
 
 int launch_unet_fused(const FusedArgs &a, hipStream_t s) {
-  static std::once_flag attr_once;
-  static int attr_status = DT_OK;
-  std::call_once(attr_once, [] {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&unet_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) attr_status = (int)e;
-  });
-  if (attr_status != DT_OK) return attr_status;
+  // the runtime keeps the dynamic-LDS attribute per device: set on the first launch on each device (launches come from several host threads)
+  constexpr int kMaxDevices = 64;
+  static std::mutex attr_mu;
+  static int attr_status[kMaxDevices];   // 0 not set yet, 1 set, otherwise -(hip error)
+  int dev = 0;
+  DT_HIP_TRY(hipGetDevice(&dev));
+  if (dev < 0 || dev >= kMaxDevices) return DT_E_ARG;
+  {
+    std::lock_guard<std::mutex> lock(attr_mu);
+    if (attr_status[dev] == 0) {
+      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&unet_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      attr_status[dev] = e == hipSuccess ? 1 : -(int)e;
+    }
+    if (attr_status[dev] != 1) return -attr_status[dev];
+  }
   if (a.G != 2 || a.n_ops < 1 || !a.ops) return DT_E_ARG;      // (the kernel's update slots per thread are sized for G = 2)
   if (a.mode == FUSED_LOOP && (a.n_steps < 1 || a.n_steps > kFusedMaxSteps)) return DT_E_ARG;
   const size_t lds = (size_t)a.lds.total * sizeof(float);

@@ -1,0 +1,48 @@
+"""No K-split instantiation of the strip kernel may spill: tools/kernel_resources.py compiles csrc/dt_conv_strip.hip
+device-only for gfx950 and reads the compiler's own resource remarks (nothing is run, no GPU needed).  Every
+conv_strip_bf16x6_kernel<BM, BN, KC, WK> with WK > 1 must report 0
+spilled VGPRs and 0 bytes of scratch: scratch traffic inside a K walk hides what the walk costs."""
+import importlib.util
+import os
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _tool():
+    spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(ROOT, "tools", "kernel_resources.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def _have_hipcc():
+    from distillation_trajectories_amd.csrc.build import hipcc_path
+    try:
+        hipcc_path()
+    except RuntimeError:
+        return False
+    return True
+
+
+def test_short_name():
+    tool = _tool()
+    assert tool.short_name("_ZN2dt24conv_strip_bf16x6_kernelILi64ELi64ELi4ELi4EEEvNS_10ConvParamsE") == "conv_strip_bf16x6_kernel<64,64,4,4>"
+    assert tool.short_name("_ZN2dt22splitk_epilogue_kernelILi8ELb1EEEvNS_10ConvParamsE") == "splitk_epilogue_kernel<8,1>"
+    assert tool.short_name("_ZN2dt14fold_bn_kernelEPKfS1_S1_S1_S1_PfS2_ii") == "fold_bn_kernel"
+    assert tool.strip_template_args("conv_strip_bf16x6_kernel<64,128,2,2>") == (64, 128, 2, 2)
+    assert tool.strip_template_args("fold_bn_kernel") is None
+
+
+@pytest.mark.skipif(not _have_hipcc(), reason="hipcc is not installed")
+def test_k_split_strip_kernels_do_not_spill():
+    tool = _tool()
+    res = tool.kernel_resources("dt_conv_strip.hip")
+    ksplit = {name: r for name, r in res.items() if (tool.strip_template_args(name) or (0, 0, 0, 1, 0))[3] > 1}
+    for name, r in sorted(ksplit.items()):
+        print(f"{name}: {r['vgprs']} VGPRs, {r['vgpr_spill']} spilled, {r['scratch_bytes']} B scratch")
+    forms = {tool.strip_template_args(n) for n in ksplit}
+    assert forms == {(64, 128, 2, 2), (128, 64, 2, 2), (64, 64, 4, 4)}, forms
+    bad = {n: (r["vgpr_spill"], r["scratch_bytes"]) for n, r in ksplit.items() if r["vgpr_spill"] or r["scratch_bytes"]}
+    assert not bad, f"(spilled VGPRs, scratch bytes per lane): {bad}"
