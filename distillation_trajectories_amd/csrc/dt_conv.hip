@@ -21,11 +21,13 @@ namespace dt {
 
 template <int BM, int BN>
 __global__ __launch_bounds__(256, 4) void conv_gemm_kernel(const ConvParams p) {
-  constexpr int WN = 2;                         // 2x2 waves
-  constexpr int MI = BM / 64, NI = BN / 64;     // 32x32 MFMA tiles per wave in m / n
+  constexpr ConvForm F = *find_conv_form(KIND_FP32, BM, BN);
+  constexpr int WN = F.wn();                    // 2x2 waves
+  constexpr int MI = F.mi(), NI = F.ni();       // 32x32 MFMA tiles per wave in m / n
   constexpr int A_PER = BM / 64, B_PER = BN / 64;  // float4 staged per thread
   constexpr int STAGE = (BM + BN) * 16;         // floats per LDS stage
-  constexpr int LDS_FLOATS = 2 * STAGE > epilogue_stage_floats<BN>() ? 2 * STAGE : epilogue_stage_floats<BN>();
+  constexpr int LDS_FLOATS = 2 * STAGE > F.stage_floats() ? 2 * STAGE : F.stage_floats();
+  static_assert(F.wm() == 2 && WN == 2 && MI * 64 == BM && NI * 64 == BN && LDS_FLOATS >= F.stage_floats(), "wave layout, epilogue stage");
   __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -135,73 +137,37 @@ __global__ __launch_bounds__(256, 4) void conv_gemm_kernel(const ConvParams p) {
     __syncthreads();
   }
 
-  conv_epilogue<MI, NI>(p, acc, lds, m0, n0, wm, wn, half, l31);
+  conv_epilogue<BM, BN, 1>(p, acc, lds, m0, n0, wm, wn, half, l31);
 }
 
 int launch_splitk_epilogue(const ConvParams &p, hipStream_t s);
+
+#define DT_GEMM_ROW(cls, kind, bm, bn, kc, wk) {{kind, bm, bn, kc, wk, cls}, conv_gemm_kernel<bm, bn>},
+static const ConvKernel kGemmKernels[] = {DT_CONV_FORMS_FP32(DT_GEMM_ROW)};
 
 int launch_conv(const ConvParams &p, hipStream_t s) {
   if (!p.in || !p.w || !p.scale || !p.shift || !p.out) return DT_E_NULL;
   if (p.cin_p % 16 || p.cout_p % 16 || p.n_p % kNPad || p.M <= 0) return DT_E_SHAPE;
   if ((long long)p.M * p.cin_p >= (1ll << 31) || (long long)p.M * p.cout_p * (p.n_dup > 1 ? p.n_dup : 1) >= (1ll << 31)) return DT_E_SHAPE;
   if (const int st = conv_admissible(p)) return st;
-  const bool tall_m = p.bm == 128, wide_n = p.bn == 128;
-  dim3 grid((p.M + p.bm - 1) / p.bm, p.n_p / p.bn, p.splits);
-  // algorithmic flops: what the reference's conv2d does on the unpadded shape (all ksize^2 taps)
-  const double flops = 2.0 * p.M * (double)p.cout_real * ((double)p.cin_real * p.ksize * p.ksize + (p.in2 ? p.cin2_real : 0));
-  if (is_strip(p.kind)) {
-    ProfileScope prof(p.kind == KIND_STRIPK ? (tall_m ? KC_CONVS_K128x64 : (wide_n ? KC_CONVS_K64x128 : KC_CONVS_K64x64)) : p.bm == 256 ? KC_CONVS_256x64 : tall_m ? (wide_n ? KC_CONVS_128x128 : KC_CONVS_128x64) : (wide_n ? KC_CONVS_64x128 : KC_CONVS_64x64),
-                      flops, 4.0 * p.M * ((double)p.cin_real + p.cout_real), s);
-    const int st = launch_conv_strip(p, s);
-    if (st) return st;
-  } else if (p.kind == KIND_BF16) {
-    ProfileScope prof(tall_m ? (wide_n ? KC_CONVB_128x128 : KC_CONVB_128x64) : (wide_n ? KC_CONVB_64x128 : KC_CONVB_64x64),
-                      flops, 4.0 * p.M * ((double)p.cin_real + p.cout_real), s);
-    const int st = launch_conv_bf16x6(p, p.bm, p.bn, s);
-    if (st) return st;
-  } else {
-    ProfileScope prof(tall_m ? (wide_n ? KC_CONV_128x128 : KC_CONV_128x64) : (wide_n ? KC_CONV_64x128 : KC_CONV_64x64),
-                      flops, 4.0 * p.M * ((double)p.cin_real + p.cout_real), s);
-    if (tall_m && wide_n) conv_gemm_kernel<128, 128><<<grid, 256, 0, s>>>(p);
-    else if (tall_m) conv_gemm_kernel<128, 64><<<grid, 256, 0, s>>>(p);
-    else if (wide_n) conv_gemm_kernel<64, 128><<<grid, 256, 0, s>>>(p);
-    else conv_gemm_kernel<64, 64><<<grid, 256, 0, s>>>(p);
-    DT_LAUNCH_CHECK();
+  {
+    // algorithmic flops: what the reference's conv2d does on the unpadded shape (all ksize^2 taps)
+    const double flops = 2.0 * p.M * (double)p.cout_real * ((double)p.cin_real * p.ksize * p.ksize + (p.in2 ? p.cin2_real : 0));
+    ProfileScope prof(find_conv_form(p.kind, p.bm, p.bn)->cls, flops, 4.0 * p.M * ((double)p.cin_real + p.cout_real), s);
+    if (p.kind == KIND_FP32) {
+      conv_kernel_of(kGemmKernels, p).fn<<<dim3((p.M + p.bm - 1) / p.bm, p.n_p / p.bn, p.splits), 256, 0, s>>>(p);
+      DT_LAUNCH_CHECK();
+    } else if (const int st = is_strip(p.kind) ? launch_conv_strip(p, s) : launch_conv_bf16x6(p, s)) return st;
   }
-  if (p.splits > 1) return launch_splitk_epilogue(p, s);
-  return DT_OK;
+  return p.splits > 1 ? launch_splitk_epilogue(p, s) : DT_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
-// Launch rules.  A new kind or tile is a change here (vocabulary, resolution, admissibility) plus its launcher.
-
-// chunks per step of a strip kind: KIND_STRIP 1, KIND_STRIP2 2, KIND_STRIPK (K split across the waves) 4 waves x 1 chunk on
-// the 64 x 64 tile, 2 waves x 1 chunk on the 128 x 64 and 64 x 128 tiles
-int strip_kc(int kind, int bm, int bn) { return kind == KIND_STRIPK ? (bm == 64 && bn == 64 ? 4 : 2) : (kind == KIND_STRIP2 ? 2 : 1); }
-
-size_t strip_lds_bytes(int W, int bm, int bn, int kind) {
-  const int kc = strip_kc(kind, bm, bn);
-  const int R = bm + 2 * strip_halo(W, bm);
-  // the strip's three planes per chunk; the double-buffered weight tile unless the waves take their fragments from global memory (K split)
-  const size_t loop = (size_t)kc * ((size_t)3 * (((R + 7) & ~7) + 8) * 16 + (kind == KIND_STRIPK ? 0 : (size_t)2 * 3 * bn * 16)) * sizeof(__bf16);
-  // the staged epilogue reuses the same LDS: WM * 32 rows per copy, one copy per K-split wave (128 rows in every K-split layout but 64 x 128)
-  const size_t stage = (size_t)(bm == 256 || (kind == KIND_STRIPK && bn == 64) ? 128 : 64) * (bn + 4) * sizeof(float);
-  return loop > stage ? loop : stage;
-}
-
-// 2 (3) strip items per thread cover BM + 2(W+1) <= 256 (384) rows; the smallest strip tile fits LDS on such rows
-bool strip_reaches(int W) { return W + 1 <= 64 && strip_lds_bytes(W, 64, 64, KIND_STRIP) <= strip_lds_limit(KIND_STRIP); }
-
-// whether kind exists and has a bm x bn tile: 64 / 128 x 64 / 128 in every kind; 256 x 64 (4 x 1 wave layout) in the strip
-// kinds; with the K split across the waves only the tiles below 128 x 128
-static bool kind_has_tile(int kind, int bm, int bn) {
-  if (kind < KIND_FP32 || kind > KIND_STRIPK || kind == 2) return false;
-  if ((bm != 64 && bm != 128 && !(bm == 256 && bn == 64 && is_strip(kind))) || (bn != 64 && bn != 128)) return false;
-  return !(kind == KIND_STRIPK && (bm > 128 || (bm == 128 && bn == 128)));
-}
+// Launch rules: vocabulary, resolution, admissibility.  Which forms exist, and what each needs, is the table's
+// (dt_conv_forms.h): a new tile of an existing kind is a row there; a new kind is a row, its rules here and its launcher.
 
 bool conv_choice_valid(const ConvChoice &c, int slot, int n_p) {
-  if (!kind_has_tile(c.kind, c.bm, c.bn) || n_p % c.bn) return false;
+  if (!find_conv_form(c.kind, c.bm, c.bn) || n_p % c.bn) return false;
   if (c.splits < 1 || c.splits > 9 || c.splits == 5 || c.splits == 6 || c.splits == 7) return false;
   return !c.fuse || (slot == 2 && c.splits == 1);
 }
@@ -233,10 +199,11 @@ ConvChoice resolve_conv_choice(const ConvLayer &L, const ConvChoice *req, int pr
   }
   if (c.kind == 2) c.kind = KIND_BF16;
   if (is_strip(c.kind) && (L.taps != 9 || !strip_reaches(L.W))) c.kind = KIND_BF16;   // full 3x3 walks of rows <= 63 px only
-  if (c.kind == KIND_STRIPK && (c.bm > 128 || (c.bm == 128 && c.bn == 128))) c.kind = KIND_STRIP2;
-  if (c.bm == 256 && !is_strip(c.kind)) c.bm = 128;
+  if (c.kind == KIND_STRIPK && !find_conv_form(c.kind, c.bm, c.bn)) c.kind = KIND_STRIP2;   // tiles the K split does not have
+  if (c.bm == 256 && !find_conv_form(c.kind, c.bm, c.bn)) c.bm = 128;                          // 256 rows: strip kinds only
   if (!L.splittable) c.splits = 1;
-  if (is_strip(c.kind) ? !chunks_fit(cc, pack_chunks(L.cin_p), c.splits * strip_kc(c.kind, c.bm, c.bn)) : (L.taps * cc) % c.splits != 0)
+  const ConvForm *f = find_conv_form(c.kind, c.bm, c.bn);   // (nullptr: a request outside the vocabulary, refused at the launch)
+  if (is_strip(c.kind) ? !chunks_fit(cc, pack_chunks(L.cin_p), c.splits * (f ? f->kc : 1)) : (L.taps * cc) % c.splits != 0)
     c.splits = 1;
   c.fuse = L.foldable && c.fuse && c.splits == 1;
   return c;
@@ -244,17 +211,15 @@ ConvChoice resolve_conv_choice(const ConvLayer &L, const ConvChoice *req, int pr
 
 int conv_admissible(const ConvParams &p) {
   const int cc = p.cin_p >> 4;
-  if (!kind_has_tile(p.kind, p.bm, p.bn) || p.n_p % p.bn) return DT_E_ARG;
+  const ConvForm *f = find_conv_form(p.kind, p.bm, p.bn);
+  if (!f || p.n_p % p.bn) return DT_E_ARG;
   if (p.splits < 1 || (p.splits > 1 && !p.slab)) return DT_E_ARG;
   if (p.ccw < cc || (p.in2 && p.ccw2 < (p.cin2_p >> 4))) return DT_E_ARG;   // weight chunks per tap of the pack in use
   if (p.in2 && (p.splits != 1 || !p.w2 || !p.bias2 || p.cin2_p % 16)) return DT_E_ARG;
   if (!is_strip(p.kind)) return (p.tap_hi - p.tap_lo) * cc % p.splits ? DT_E_ARG : DT_OK;
-  const int kc = strip_kc(p.kind, p.bm, p.bn);
-  if (p.ksize != 3 || p.tap_lo != 0 || p.tap_hi != 9 || !chunks_fit(cc, p.ccw, p.splits * kc)) return DT_E_ARG;
-  if (kc == 4 && p.W + 1 > 32) return DT_E_SHAPE;                  // one strip item per thread: BM + 2(W+1) <= 128 rows
-  if (p.in2 && !chunks_fit(p.cin2_p >> 4, p.ccw2, kc)) return DT_E_ARG;
-  if (p.W + 1 > 64) return DT_E_SHAPE;
-  return strip_lds_bytes(p.W, p.bm, p.bn, p.kind) <= strip_lds_limit(p.kind) ? DT_OK : DT_E_SHAPE;
+  if (p.ksize != 3 || p.tap_lo != 0 || p.tap_hi != 9 || !chunks_fit(cc, p.ccw, p.splits * f->kc)) return DT_E_ARG;
+  if (p.in2 && !chunks_fit(p.cin2_p >> 4, p.ccw2, f->kc)) return DT_E_ARG;
+  return f->reaches(p.W) ? DT_OK : DT_E_SHAPE;
 }
 
 // sum of the split-K slabs in z order + the layer epilogue, float4 over channels.  S = compile-time slab count

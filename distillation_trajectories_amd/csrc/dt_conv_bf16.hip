@@ -26,8 +26,10 @@ namespace dt {
 //  and are not built.
 template <int BM, int BN>
 __global__ __launch_bounds__(256, BM * BN > 128 * 128 ? 2 : 3) void conv_gemm_bf16x6_kernel(const ConvParams p) {
-  constexpr int WM = 2, WN = 2;                                   // 2x2 waves
-  constexpr int MI = BM / (32 * WM), NI = BN / (32 * WN);
+  constexpr ConvForm F = *find_conv_form(KIND_BF16, BM, BN);
+  constexpr int WM = F.wm(), WN = F.wn();                          // 2x2 waves
+  constexpr int MI = F.mi(), NI = F.ni();
+  static_assert(WM == 2 && WN == 2 && MI * 64 == BM && NI * 64 == BN, "wave layout");
   constexpr int PLANE_A = BM * 16, PLANE_B = BN * 16;            // bf16 elements per plane per stage
   constexpr int STAGE = 3 * (PLANE_A + PLANE_B);                  // bf16 elements per stage
   __shared__ __attribute__((aligned(16))) __bf16 lds[2 * STAGE];
@@ -144,17 +146,7 @@ __global__ __launch_bounds__(256, BM * BN > 128 * 128 ? 2 : 3) void conv_gemm_bf
         for (int pl = 0; pl < 3; ++pl)
           fa[pl] = *reinterpret_cast<const bf16x8 *>(A + pl * PLANE_A + a_frag[mi]);
 #pragma unroll
-        for (int ni = 0; ni < NI; ++ni) {
-          // smallest terms first so their sum is formed before it meets the large partial sums
-          f32x16 c = acc[mi][ni];
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[2], fb[ni][0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[ni][1], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[ni][2], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[ni][0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[ni][1], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[ni][0], c, 0, 0, 0);
-          acc[mi][ni] = c;
-        }
+        for (int ni = 0; ni < NI; ++ni) mfma_bf16x6(acc[mi][ni], fa, fb[ni]);
       }
     }
     if (more) {
@@ -177,16 +169,15 @@ __global__ __launch_bounds__(256, BM * BN > 128 * 128 ? 2 : 3) void conv_gemm_bf
     }
     __syncthreads();
   }
-  static_assert(2 * STAGE * sizeof(__bf16) >= epilogue_stage_floats<BN>() * sizeof(float), "epilogue stage");
-  conv_epilogue<MI, NI>(p, acc, reinterpret_cast<float *>(lds), m0, n0, wm, wn, half, l31);
+  static_assert(2 * STAGE * sizeof(__bf16) >= F.stage_bytes(), "epilogue stage");
+  conv_epilogue<BM, BN, 1>(p, acc, reinterpret_cast<float *>(lds), m0, n0, wm, wn, half, l31);
 }
 
-int launch_conv_bf16x6(const ConvParams &p, int bm, int bn, hipStream_t s) {
-  dim3 grid((p.M + bm - 1) / bm, p.n_p / bn, p.splits);
-  if (bm == 128 && bn == 128) conv_gemm_bf16x6_kernel<128, 128><<<grid, 256, 0, s>>>(p);
-  else if (bm == 128) conv_gemm_bf16x6_kernel<128, 64><<<grid, 256, 0, s>>>(p);
-  else if (bn == 128) conv_gemm_bf16x6_kernel<64, 128><<<grid, 256, 0, s>>>(p);
-  else conv_gemm_bf16x6_kernel<64, 64><<<grid, 256, 0, s>>>(p);
+#define DT_BF16_ROW(cls, kind, bm, bn, kc, wk) {{kind, bm, bn, kc, wk, cls}, conv_gemm_bf16x6_kernel<bm, bn>},
+static const ConvKernel kBf16Kernels[] = {DT_CONV_FORMS_BF16(DT_BF16_ROW)};
+
+int launch_conv_bf16x6(const ConvParams &p, hipStream_t s) {
+  conv_kernel_of(kBf16Kernels, p).fn<<<dim3((p.M + p.bm - 1) / p.bm, p.n_p / p.bn, p.splits), 256, 0, s>>>(p);
   DT_LAUNCH_CHECK();
   return DT_OK;
 }

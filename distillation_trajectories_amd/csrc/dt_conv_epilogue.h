@@ -29,10 +29,18 @@ __device__ inline void split8(const f32x4 lo, const f32x4 hi, bf16x8 &p1, bf16x8
   }
 }
 
-// floats of LDS the staged epilogue needs for a BN-column tile: WM * 32 rows (one 32-row accumulator tile of each
-// wave row; the four waves sit WM x 4/WM over the tile) at a pitch of BN + 4 floats
-template <int BN, int WM = 2>
-constexpr int epilogue_stage_floats() { return WM * 32 * (BN + 4); }
+// The six plane products of one 32 x 32 x 16 split-bf16 step (planes 0..2 = leading, second, third part of the operands),
+// smallest terms first so their sum is formed before it meets the large partial sums
+__device__ inline void mfma_bf16x6(f32x16 &acc, const bf16x8 (&fa)[3], const bf16x8 (&fb)[3]) {
+  f32x16 c = acc;
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[2], fb[0], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[1], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[2], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[0], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[1], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[0], c, 0, 0, 0);
+  acc = c;
+}
 
 // Epilogue of every convolution kernel, staged through LDS.
 //
@@ -44,7 +52,7 @@ constexpr int epilogue_stage_floats() { return WM * 32 * (BN + 4); }
 // row segment per 32 lanes: every side input is one batched float4 load per unit, every store is 16 bytes per lane,
 // and the mode flags are tested per pass, not per element.
 //
-// `stage` is any LDS the kernel no longer needs (>= epilogue_stage_floats<BN>() floats); every wave of the
+// `stage` is any LDS the kernel no longer needs (>= the form's stage_floats() floats); every wave of the
 // workgroup must call this (it contains barriers).  Per row m and channel n:
 //   v = in2 ? acc + bias2 : relu?(acc * scale + shift);  v += time bias row;  v += residual;  v += x3 skip;
 //   out = v;  pool_out = 2x2 max of v (32-row tiles hold whole row pairs for W <= 16);  head_out = 1x1 head of v.
@@ -57,11 +65,13 @@ constexpr int epilogue_stage_floats() { return WM * 32 * (BN + 4); }
 //
 // WK > 1 (strip kernel with the K split across waves): WK waves hold partial sums of the same tile; each writes its own
 // copy of the stage and a unit is the sum of the copies in wave order (deterministic).
-template <int MI, int NI, int WM = 2, int WK = 1>
+template <int BM, int BN, int WK, int MI, int NI>
 __device__ inline void conv_epilogue(const ConvParams &p, f32x16 (&acc)[MI][NI], float *stage, int m0, int n0, int wm, int wn,
                                      int half, int l31, int wk = 0) {
-  constexpr int BN = NI * 32 * (4 / (WM * WK)), P = BN + 4, C4 = BN / 4, U = WM * C4 / 8;   // U float4 units per thread and pass
-  constexpr int COPY = WM * 32 * P;
+  constexpr ConvForm F = *find_conv_layout(BM, BN, WK);
+  static_assert(MI == F.mi() && NI == F.ni(), "accumulator tiles of the form");
+  constexpr int WM = F.wm(), P = F.pitch(), C4 = BN / 4, U = WM * C4 / 8;   // U float4 units per thread and pass
+  constexpr int COPY = F.copy_floats();
   const int tid = threadIdx.x;
   const int HW = p.H * p.W;
   // pictures are powers of two in every benchmark shape: row -> (picture, y, x) by shifts there (an integer division by a run-time

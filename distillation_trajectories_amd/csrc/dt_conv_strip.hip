@@ -35,23 +35,25 @@ extern __shared__ __attribute__((aligned(16))) __bf16 strip_lds[];
 // small workgroup tiles to fill the chip, and a 64 x 64 tile cut 2 x 2 leaves each wave 32 x 32 (6 fragment reads per
 // 6 MFMAs, ~100 TF/s).  With WK = 4 every wave keeps a 64 x 64 accumulator (12 reads per 24 MFMAs) over a quarter of
 // the channels and the four partial tiles are summed in wave order in the staged epilogue -- split-K without slabs.
-template <int BM, int BN, int KC = 1, int WK = 1>
-__global__ __launch_bounds__(256, KC == 1 ? 3 : 2) void conv_strip_bf16x6_kernel(const ConvParams p) {
+template <int BM, int BN, int KC, int WK>
+__global__ __launch_bounds__(256, find_strip_form(BM, BN, KC, WK)->waves_per_simd()) void conv_strip_bf16x6_kernel(const ConvParams p) {
   // four waves: 2 x 2 over the tile, or 4 x 1 for the 256 x 64 tile (a 64 x 64 wave tile -- 12 fragment reads per 24
   // MFMAs, like the 128 x 128 tile -- for layers with 64 output channels, where 128 x 64 leaves each wave 64 x 32),
   // or WM x 1 x WK with the K split
-  constexpr int WN = WK > 1 ? BN / 64 : (BM == 256 ? 1 : 2), WM = 4 / (WN * WK), NT = 256;
-  constexpr int MI = BM / (32 * WM), NI = BN / (32 * WN);
-  constexpr int KW = KC / WK;                                      // chunks of a step one wave multiplies
-  static_assert(KC % WK == 0 && MI * 32 * WM == BM && NI * 32 * WN == BN && (WK == 1 || (MI == 2 && NI == 2)), "wave layout");
-  constexpr int PLANE_B = BN * 16, STAGE_B = 3 * PLANE_B;         // bf16 elements
-  constexpr int AP = BM == 256 ? 3 : (KC == 4 ? 1 : 2);            // strip items (row, k-half) per thread (K = 64 steps: rows of at most 31 px)
+  constexpr ConvForm F = *find_strip_form(BM, BN, KC, WK);
+  constexpr int WN = F.wn(), WM = F.wm(), NT = 256;
+  constexpr int MI = F.mi(), NI = F.ni();
+  constexpr int KW = F.kw();                                       // chunks of a step one wave multiplies
+  static_assert(WM * WN * WK * 64 == NT && KC % WK == 0 && MI * 32 * WM == BM && NI * 32 * WN == BN && (WK == 1 || (MI == 2 && NI == 2)), "wave layout");
+  constexpr int PLANE_B = F.plane_b(), STAGE_B = 3 * PLANE_B;     // bf16 elements
+  constexpr int AP = F.ap();                                       // strip items (row, k-half) per thread
+  static_assert(2 * (BM + 2 * (F.max_w() + 1)) <= AP * NT, "strip staging reach");
   const int halo = strip_halo(p.W, BM);
-  const int R = BM + 2 * halo;                                     // strip rows
-  const int RZ = (R + 7) & ~7;                                     // 8 all-zero rows start here (multiple of 8)
-  const int PLANE_A = (RZ + 8) * 16;
+  const int R = F.strip_rows(halo);
+  const int RZ = F.zero_row(R);                                    // 8 all-zero rows start here (multiple of 8)
+  const int PLANE_A = F.plane_a(RZ);
   __bf16 *As = strip_lds;                                          // [KC][3][RZ+8][16]
-  __bf16 *Bs = strip_lds + KC * 3 * PLANE_A;                       // [2][KC][3][BN][16]
+  __bf16 *Bs = strip_lds + F.strip_elems(PLANE_A);                 // [2][KC][3][BN][16]
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);       // wave-uniform: chunk and tile offsets stay in scalar registers
@@ -276,17 +278,7 @@ __global__ __launch_bounds__(256, KC == 1 ? 3 : 2) void conv_strip_bf16x6_kernel
           for (int pl = 0; pl < 3; ++pl)
             fa[pl] = *reinterpret_cast<const bf16x8 *>(A + pl * PLANE_A + a_e[mi]);
 #pragma unroll
-          for (int ni = 0; ni < NI; ++ni) {
-            // smallest terms first so their sum is formed before it meets the large partial sums
-            f32x16 c = acc[mi][ni];
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[2], fb[ni][0], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[ni][1], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[ni][2], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[ni][0], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[ni][1], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[ni][0], c, 0, 0, 0);
-            acc[mi][ni] = c;
-          }
+          for (int ni = 0; ni < NI; ++ni) mfma_bf16x6(acc[mi][ni], fa, fb[ni]);
         }
       }
     }
@@ -351,16 +343,7 @@ __global__ __launch_bounds__(256, KC == 1 ? 3 : 2) void conv_strip_bf16x6_kernel
         bf16x8 fa[3];
         split8(g[kw][mi][0], g[kw][mi][1], fa[0], fa[1], fa[2]);
 #pragma unroll
-        for (int ni = 0; ni < NI; ++ni) {
-          f32x16 c = acc[mi][ni];
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[2], fb[ni][0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[ni][1], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[ni][2], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[ni][0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[ni][1], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[ni][0], c, 0, 0, 0);
-          acc[mi][ni] = c;
-        }
+        for (int ni = 0; ni < NI; ++ni) mfma_bf16x6(acc[mi][ni], fa, fb[ni]);
       }
     }
     if (s2 + 2 < n_skip) load_a(g, s2 + 2);
@@ -411,7 +394,7 @@ __global__ __launch_bounds__(256, KC == 1 ? 3 : 2) void conv_strip_bf16x6_kernel
     if (p.in2) {
       // BN + ReLU apply to the COMPLETE 3x3 sum: the WK partial tiles meet in LDS (free after the last step's barrier), wave
       // 0 of each group continues with relu(bn(sum)) and the others with zero, and the skip walk restarts the pipeline
-      constexpr int P = BN + 4, COPY = WM * 32 * P;
+      constexpr int P = F.pitch(), COPY = F.copy_floats();
       float *red = reinterpret_cast<float *>(strip_lds);
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi) {
@@ -458,11 +441,14 @@ __global__ __launch_bounds__(256, KC == 1 ? 3 : 2) void conv_strip_bf16x6_kernel
     for (int ch = n_main; ch < n_chunks; ++ch)                     // fused 1x1 skip walk through the strip: centre tap only
       do_step(std::integral_constant<int, 4>{}, ch, true, true, ch + 1 < n_chunks, ADV_SKIP);
   }
-  conv_epilogue<MI, NI, WM, WK>(p, acc, reinterpret_cast<float *>(strip_lds), m0, n0, wm, wn, half, l31, wk);
+  conv_epilogue<BM, BN, WK>(p, acc, reinterpret_cast<float *>(strip_lds), m0, n0, wm, wn, half, l31, wk);
 }
 
-// The K = 32 instantiations take up to 96 KB of dynamic LDS (128x128: 80 KB).  The runtime keeps that attribute per device: it
-// is set on the first such launch on each device, not once per process.
+#define DT_STRIP_ROW(cls, kind, bm, bn, kc, wk) {{kind, bm, bn, kc, wk, cls}, conv_strip_bf16x6_kernel<bm, bn, kc, wk>},
+static const ConvKernel kStripKernels[] = {DT_CONV_FORMS_ALL_STRIP(DT_STRIP_ROW)};
+
+// The forms with more than one chunk per step take up to 96 KB of dynamic LDS (128x128: 80 KB).  The runtime keeps that
+// attribute per device: it is set on the first such launch on each device, not once per process.
 static int strip_lds_attribute() {
   constexpr int kMaxDevices = 64;
   static std::mutex mu;                    // launches come from several host threads
@@ -472,58 +458,26 @@ static int strip_lds_attribute() {
   if (dev < 0 || dev >= kMaxDevices) return DT_E_ARG;
   std::lock_guard<std::mutex> lock(mu);
   if (status[dev] == 0) {
-    const void *fns[8] = {reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<64, 128, 2, 2>),
-                          reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<64, 64, 4, 4>),
-                          reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<128, 64, 2, 2>),
-                          reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<256, 64, 2>),
-                          reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<128, 128, 2>),
-                          reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<128, 64, 2>),
-                          reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<64, 128, 2>),
-                          reinterpret_cast<const void *>(&conv_strip_bf16x6_kernel<64, 64, 2>)};
     status[dev] = 1;
-    for (const void *f : fns) {
-      const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 98304);
+    for (const ConvKernel &k : kStripKernels) {
+      if (!k.form.needs_lds_attribute()) continue;
+      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.form.lds_limit());
       if (e != hipSuccess) status[dev] = -(int)e;
     }
   }
   return status[dev] == 1 ? DT_OK : -status[dev];
 }
 
-// p passed conv_admissible (dt_conv.hip): a full 3x3 walk whose tile, chunk groups and LDS footprint the kind supports
+// p passed conv_admissible (dt_conv.hip): a full 3x3 walk whose tile, chunk groups and LDS footprint the form supports
 int launch_conv_strip(const ConvParams &p_in, hipStream_t s) {
   ConvParams p = p_in;
-  const int bm = p.bm, bn = p.bn, kind = p.kind;
-  const int kc = strip_kc(kind, bm, bn);
-  dim3 grid((p.M + bm - 1) / bm, p.n_p / bn, p.splits);
-  size_t lds = strip_lds_bytes(p.W, bm, bn, kind);
-  p.dup_stage2 = 0;
-  if (p.n_dup == 2 && p.pool_out) {   // a second epilogue stage behind the first (and its K-split copies), if it fits this launch's LDS class
-    const size_t rows1 = bm == 256 || kc == 4 || (kind == KIND_STRIPK && bm == 128) ? 128 : 64;   // WK * WM * 32
-    const size_t rows2 = bm == 256 ? 128 : (bm == 128 ? 64 : 32);                                 // WM * 32
-    const size_t need = (rows1 + (kind == KIND_STRIPK ? rows2 : rows1)) * (bn + 4) * sizeof(float);
-    if (need <= strip_lds_limit(kind)) {
-      p.dup_stage2 = 1;
-      if (need > lds) lds = need;
-    }
-  }
-  if (kind != KIND_STRIP) {
-    if (const int st = strip_lds_attribute()) return st;
-    if (kind == KIND_STRIPK && bn == 128) conv_strip_bf16x6_kernel<64, 128, 2, 2><<<grid, 256, lds, s>>>(p);
-    else if (kind == KIND_STRIPK && bm == 64) conv_strip_bf16x6_kernel<64, 64, 4, 4><<<grid, 256, lds, s>>>(p);
-    else if (kind == KIND_STRIPK) conv_strip_bf16x6_kernel<128, 64, 2, 2><<<grid, 256, lds, s>>>(p);
-    else if (bm == 256) conv_strip_bf16x6_kernel<256, 64, 2><<<grid, 256, lds, s>>>(p);
-    else if (bm == 128 && bn == 128) conv_strip_bf16x6_kernel<128, 128, 2><<<grid, 256, lds, s>>>(p);
-    else if (bm == 128) conv_strip_bf16x6_kernel<128, 64, 2><<<grid, 256, lds, s>>>(p);
-    else if (bn == 128) conv_strip_bf16x6_kernel<64, 128, 2><<<grid, 256, lds, s>>>(p);
-    else conv_strip_bf16x6_kernel<64, 64, 2><<<grid, 256, lds, s>>>(p);
-    DT_LAUNCH_CHECK();
-    return DT_OK;
-  }
-  if (bm == 256) conv_strip_bf16x6_kernel<256, 64><<<grid, 256, lds, s>>>(p);
-  else if (bm == 128 && bn == 128) conv_strip_bf16x6_kernel<128, 128><<<grid, 256, lds, s>>>(p);
-  else if (bm == 128) conv_strip_bf16x6_kernel<128, 64><<<grid, 256, lds, s>>>(p);
-  else if (bn == 128) conv_strip_bf16x6_kernel<64, 128><<<grid, 256, lds, s>>>(p);
-  else conv_strip_bf16x6_kernel<64, 64><<<grid, 256, lds, s>>>(p);
+  const ConvKernel &k = conv_kernel_of(kStripKernels, p);
+  size_t lds = k.form.lds_bytes(p.W);
+  // a second epilogue stage behind the first (and its K-split copies), if it fits this launch's LDS class
+  p.dup_stage2 = p.n_dup == 2 && p.pool_out && k.form.dup_stage_bytes() <= k.form.lds_limit();
+  if (p.dup_stage2 && k.form.dup_stage_bytes() > lds) lds = k.form.dup_stage_bytes();
+  if (const int st = k.form.needs_lds_attribute() ? strip_lds_attribute() : DT_OK) return st;
+  k.fn<<<dim3((p.M + p.bm - 1) / p.bm, p.n_p / p.bn, p.splits), 256, lds, s>>>(p);
   DT_LAUNCH_CHECK();
   return DT_OK;
 }

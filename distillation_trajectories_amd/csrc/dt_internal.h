@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/dt_hip.h"
+#include "dt_conv_forms.h"
 
 #define DT_HIP_TRY(expr)                         \
   do {                                           \
@@ -21,11 +22,8 @@ namespace dt {
 
 // ---- optional per-launch timing with HIP events on the launch stream (bench.py roofline numbers).
 // Off by default; when on, every instrumented launch is bracketed by two event records.
-enum KernelClass {
-  KC_CONV_128x128 = 0, KC_CONV_128x64, KC_CONV_64x128, KC_CONV_64x64,
-  KC_CONVB_128x128, KC_CONVB_128x64, KC_CONVB_64x128, KC_CONVB_64x64,
-  KC_CONVS_128x128, KC_CONVS_128x64, KC_CONVS_64x128, KC_CONVS_64x64, KC_CONVS_256x64, KC_CONVS_K128x64, KC_CONVS_K64x64, KC_CONVS_K64x128,
-  KC_SPLITK_EPILOGUE, KC_FIRST_CONV, KC_POOL, KC_UPCAT, KC_HEAD, KC_HEAD_UP, KC_TIME_BIAS, KC_UPDATE, KC_METRICS,
+enum KernelClass {   // the convolution classes come first: ConvClass (dt_conv_forms.h)
+  KC_SPLITK_EPILOGUE = KC_CONV_COUNT, KC_FIRST_CONV, KC_POOL, KC_UPCAT, KC_HEAD, KC_HEAD_UP, KC_TIME_BIAS, KC_UPDATE, KC_METRICS,
   KC_WASSERSTEIN, KC_RESAMPLE, KC_FUSED, KC_PAIR_METRICS,
   KC_COUNT
 };
@@ -64,22 +62,6 @@ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 inline bool chunks_fit(int cc, int ccw, int div) { return div >= 1 && round_up(cc, div) <= ccw; }
 // 16-channel weight chunks per tap of a split-bf16 pack of cin_p input channels (zero chunks up to a multiple of kChunkPad)
 inline int pack_chunks(int cin_p) { return round_up(cin_p, 16 * kChunkPad) >> 4; }
-
-// Launch kinds of a convolution.  The numbers are part of the ABI (dt_unet_conv_choice / dt_unet_set_conv_choice, the plan
-// table plans/gfx950.json); 2 (round 1's LDS-DMA variant) is retired and rejected.
-enum ConvKind {
-  KIND_FP32 = 0,     // exact fp32 MFMA implicit GEMM (conv_gemm_kernel)
-  KIND_BF16 = 1,     // split-bf16 implicit GEMM (conv_gemm_bf16x6_kernel)
-  KIND_STRIP = 3,    // split-bf16 strip kernel (full 3x3 walks): one 16-channel chunk per step
-  KIND_STRIP2 = 4,   // strip kernel, two chunks (K = 32) per step
-  KIND_STRIPK = 5,   // strip kernel, the step's chunks split across the waves (tiles below 128 x 128)
-};
-inline bool is_strip(int kind) { return kind >= KIND_STRIP; }
-
-// Halo rows either side of a strip tile.  The corner taps reach W + 1 pixels back / ahead; when the tile starts at x = 0 and
-// ends at x = W - 1 (BM a multiple of W) those two reads are out-of-picture taps of the first / last row and go to the
-// zero rows anyway, so W rows are enough -- which is what lets the K = 32 tile fit twice per CU at W = 16.
-__host__ __device__ inline int strip_halo(int W, int bm) { return bm % W == 0 ? W : W + 1; }
 
 // One convolution expressed as an implicit GEMM over NHWC activations:
 //   out[m][n] = epilogue( sum_{tap,c} in[pixel(m)+tap][c] * w[tap][c][n] )
@@ -152,8 +134,16 @@ struct ConvParams {
 };
 
 int launch_conv(const ConvParams &p, hipStream_t s);
-int launch_conv_bf16x6(const ConvParams &p, int bm, int bn, hipStream_t s);
-int launch_conv_strip(const ConvParams &p, hipStream_t s);    // the strip kinds; p passed conv_admissible
+int launch_conv_bf16x6(const ConvParams &p, hipStream_t s);   // KIND_BF16 and the strip kinds: p passed conv_admissible
+int launch_conv_strip(const ConvParams &p, hipStream_t s);
+// a translation unit's kernels, one per form of its lists in dt_conv_forms.h
+struct ConvKernel { ConvForm form; void (*fn)(ConvParams); };
+template <size_t N>
+inline const ConvKernel &conv_kernel_of(const ConvKernel (&table)[N], const ConvParams &p) {
+  for (const ConvKernel &k : table)
+    if (k.form.kind == p.kind && k.form.bm == p.bm && k.form.bn == p.bn) return k;
+  return table[0];   // (not reached: conv_admissible found the form)
+}
 // cin_w: padded input channels per tap of the pack (>= cin_p, multiple of 16 * kChunkPad; zeros beyond cin_p)
 int launch_pack_conv_bf16x3(const float *w_oihw, void *wp, int cout, int cin, int ksize, int cin_p, int cin_w, int n_p,
                             int split_c, int split_cp, hipStream_t s);
@@ -170,11 +160,8 @@ struct ConvLayer {
   bool splittable;    // split-K has a slab: not enc1 (its conv2 keeps the fused image-skip epilogue), M <= kSplitMaxRows
   bool foldable;      // conv2 of a block with a 1x1 skip conv (j > 0), which its K walk can take over
 };
-int strip_kc(int kind, int bm, int bn);      // 16-channel chunks per step of a strip kind
-size_t strip_lds_bytes(int W, int bm, int bn, int kind);   // dynamic LDS of a strip launch on rows of W pixels
-// dynamic LDS a strip launch may take: 64 KB for KIND_STRIP, 96 KB (two workgroups per CU) for the K = 32 kinds
-inline size_t strip_lds_limit(int kind) { return kind == KIND_STRIP ? 65536u : 98304u; }
-bool strip_reaches(int W);                   // whether some strip tile runs on rows of W pixels (staging reach, LDS)
+// whether some strip form (the smallest one) runs on rows of W pixels
+inline bool strip_reaches(int W) { return find_conv_form(KIND_STRIP, 64, 64)->reaches(W); }
 // vocabulary: what dt_unet_set_conv_choice accepts for a slot (0 skip, 1 conv1, 2 conv2) with n_p output channels
 bool conv_choice_valid(const ConvChoice &c, int slot, int n_p);
 // resolution: the choice a layer runs for a request (nullptr: the default of the precision mode DT_PREC_*); degrades what

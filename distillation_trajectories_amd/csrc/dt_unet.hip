@@ -59,15 +59,21 @@ struct Profiler {
     return pool[used++];
   }
 } g_prof;
-const char *kClassName[KC_COUNT] = {
-    "conv_gemm_kernel<128,128>", "conv_gemm_kernel<128,64>", "conv_gemm_kernel<64,128>", "conv_gemm_kernel<64,64>",
-    "conv_gemm_bf16x6_kernel<128,128>", "conv_gemm_bf16x6_kernel<128,64>", "conv_gemm_bf16x6_kernel<64,128>",
-    "conv_gemm_bf16x6_kernel<64,64>",
-    "conv_strip_bf16x6_kernel<128,128>", "conv_strip_bf16x6_kernel<128,64>", "conv_strip_bf16x6_kernel<64,128>",
-    "conv_strip_bf16x6_kernel<64,64>", "conv_strip_bf16x6_kernel<256,64>", "conv_strip_bf16x6_kernel<128,64,K2>",
-    "conv_strip_bf16x6_kernel<64,64,K4>", "conv_strip_bf16x6_kernel<64,128,K2>", "splitk_epilogue_kernel", "first_conv_kernel", "maxpool_kernel", "upcat_kernel", "head_kernel", "head_upsample_kernel",
+const char *kClassName[KC_COUNT - KC_CONV_COUNT] = {
+    "splitk_epilogue_kernel", "first_conv_kernel", "maxpool_kernel", "upcat_kernel", "head_kernel", "head_upsample_kernel",
     "time_bias_kernel", "cfg_update_kernel", "traj_metrics_kernel", "wasserstein_kernel", "resampled_distance_kernel",
     "unet_fused_kernel", "pair_metrics_kernel"};
+// the printed name of a class: a convolution class is named after the form(s) that carry it (dt_conv_forms.h)
+const char *class_name(int cls) {
+  switch (cls) {
+#define DT_GEMM(c, kind, bm, bn, kc, wk) case c: return "conv_gemm_kernel<" #bm "," #bn ">";
+#define DT_BF16(c, kind, bm, bn, kc, wk) case c: return "conv_gemm_bf16x6_kernel<" #bm "," #bn ">";
+#define DT_STRIP(c, kind, bm, bn, kc, wk) case c: return "conv_strip_bf16x6_kernel<" #bm "," #bn ">";
+#define DT_STRIPK(c, kind, bm, bn, kc, wk) case c: return "conv_strip_bf16x6_kernel<" #bm "," #bn ",K" #kc ">";
+    DT_CONV_FORMS_FP32(DT_GEMM) DT_CONV_FORMS_BF16(DT_BF16) DT_CONV_FORMS_STRIP(DT_STRIP) DT_CONV_FORMS_STRIPK(DT_STRIPK)
+    default: return kClassName[cls - KC_CONV_COUNT];
+  }
+}
 }  // namespace
 
 namespace dt {
@@ -1045,7 +1051,7 @@ int dt_profile_class_count(void) { return KC_COUNT; }
 
 int dt_profile_read(int cls, const char **name, long long *launches, double *ms, double *flops, double *bytes) {
   if (cls < 0 || cls >= KC_COUNT || !launches || !ms || !flops || !bytes) return DT_E_ARG;
-  if (name) *name = kClassName[cls];
+  if (name) *name = class_name(cls);
   *launches = 0; *ms = 0; *flops = 0; *bytes = 0;
   std::lock_guard<std::mutex> lock(g_prof.mu);
   for (const ProfRecord &r : g_prof.rec) {

@@ -1,7 +1,9 @@
 """No K-split instantiation of the strip kernel may spill: tools/kernel_resources.py compiles csrc/dt_conv_strip.hip
 device-only for gfx950 and reads the compiler's own resource remarks (nothing is run, no GPU needed).  Every
 conv_strip_bf16x6_kernel<BM, BN, KC, WK> with WK > 1 must report 0
-spilled VGPRs and 0 bytes of scratch: scratch traffic inside a K walk hides what the walk costs."""
+spilled VGPRs and 0 bytes of scratch: scratch traffic inside a K walk hides what the walk costs.
+The three conv code objects together hold exactly the 21 forms of csrc/dt_conv_forms.h."""
+import functools
 import importlib.util
 import os
 
@@ -15,6 +17,11 @@ def _tool():
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod
+
+
+@functools.lru_cache(maxsize=None)
+def _resources(source):
+    return _tool().kernel_resources(source)
 
 
 def _have_hipcc():
@@ -38,7 +45,7 @@ def test_short_name():
 @pytest.mark.skipif(not _have_hipcc(), reason="hipcc is not installed")
 def test_k_split_strip_kernels_do_not_spill():
     tool = _tool()
-    res = tool.kernel_resources("dt_conv_strip.hip")
+    res = _resources("dt_conv_strip.hip")
     ksplit = {name: r for name, r in res.items() if (tool.strip_template_args(name) or (0, 0, 0, 1, 0))[3] > 1}
     for name, r in sorted(ksplit.items()):
         print(f"{name}: {r['vgprs']} VGPRs, {r['vgpr_spill']} spilled, {r['scratch_bytes']} B scratch")
@@ -46,3 +53,18 @@ def test_k_split_strip_kernels_do_not_spill():
     assert forms == {(64, 128, 2, 2), (128, 64, 2, 2), (64, 64, 4, 4)}, forms
     bad = {n: (r["vgpr_spill"], r["scratch_bytes"]) for n, r in ksplit.items() if r["vgpr_spill"] or r["scratch_bytes"]}
     assert not bad, f"(spilled VGPRs, scratch bytes per lane): {bad}"
+
+
+TILES = [(128, 128), (128, 64), (64, 128), (64, 64)]
+FORMS = ({f"conv_gemm_kernel<{bm},{bn}>" for bm, bn in TILES} | {f"conv_gemm_bf16x6_kernel<{bm},{bn}>" for bm, bn in TILES} |
+         {f"conv_strip_bf16x6_kernel<{bm},{bn},{kc},1>" for bm, bn in TILES + [(256, 64)] for kc in (1, 2)} |
+         {"conv_strip_bf16x6_kernel<64,128,2,2>", "conv_strip_bf16x6_kernel<128,64,2,2>", "conv_strip_bf16x6_kernel<64,64,4,4>"})
+
+
+@pytest.mark.skipif(not _have_hipcc(), reason="hipcc is not installed")
+def test_conv_code_objects_hold_exactly_the_21_forms():
+    """a row dropped from (or added to) the table of forms shows here, not at a launch"""
+    import re
+    got = [n for src in ("dt_conv.hip", "dt_conv_bf16.hip", "dt_conv_strip.hip") for n in _resources(src)
+           if re.match(r"conv_\w+_kernel<", n)]
+    assert len(FORMS) == 21 and sorted(got) == sorted(FORMS), sorted(set(got) ^ FORMS)
