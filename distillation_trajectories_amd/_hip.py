@@ -16,7 +16,7 @@ PREC_FP32, PREC_SPLIT_BF16, PREC_AUTO = 0, 1, 2
 KIND_FP32 = 0
 KIND_NAMES = {KIND_FP32: "fp32", 1: "split-bf16", 3: "split-bf16-strip", 4: "split-bf16-strip32", 5: "split-bf16-stripk"}
 BT_COUNT, GT_COUNT, N_BLOCKS = 16, 9, 8
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 
 class HipLibraryError(RuntimeError):
@@ -38,24 +38,21 @@ SIGNATURES = {
     "dt_unet_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
     "dt_unet_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
                                 c_void_p, c_size_t, c_void_p]),
-    "dt_unet_autotune": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "dt_unet_conv_choice": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int),
-                                    POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
-    "dt_unet_set_conv_choice": (c_int, [c_void_p] + [c_int] * 10),
-    "dt_unet_declare_shape": (c_int, [c_void_p] + [c_int] * 5),
+    "dt_unet_autotune": (c_int, [c_void_p] + [c_int] * 5 + [c_void_p, c_size_t, c_void_p]),
+    "dt_unet_conv_choice": (c_int, [c_void_p] + [c_int] * 7 + [POINTER(c_int)] * 5),
+    "dt_unet_set_conv_choice": (c_int, [c_void_p] + [c_int] * 12),
     "dt_unet_set_precision": (c_int, [c_void_p, c_int]),
     "dt_unet_set_head_fusion": (c_int, [c_void_p, c_int]),
     "dt_unet_set_fused": (c_int, [c_void_p, c_int]),
     "dt_unet_fused_active": (c_int, [c_void_p, c_int, c_int]),
-    "dt_unet_time_conv": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                  c_void_p, c_size_t, c_void_p, POINTER(c_float), POINTER(c_double)]),
+    "dt_unet_time_conv": (c_int, [c_void_p] + [c_int] * 13 + [c_void_p, c_size_t, c_void_p, POINTER(c_float), POINTER(c_double)]),
     "dt_unet_debug_activation": (c_int, [c_void_p, c_int, c_int, c_int, c_int, POINTER(c_size_t), POINTER(c_int),
                                          POINTER(c_int), POINTER(c_int)]),
     "dt_cfg_update": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_float), c_int,
                               c_void_p, c_float, c_void_p, c_int, c_int, c_void_p]),
     "dt_sample_trajectory": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, POINTER(c_float),
                                      POINTER(c_int32), c_void_p, c_void_p, POINTER(c_int64), c_void_p, c_float,
-                                     c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+                                     c_void_p, c_void_p, c_size_t, c_void_p]),
     "dt_unet_forward_mixed": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
                                       c_void_p, c_size_t, c_void_p]),
     "dt_sample_trajectory_mixed": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,

@@ -287,7 +287,8 @@ __global__ __launch_bounds__(256) void resize_bilinear_kernel(const float *__res
   }
 }
 
-int launch_resize_bilinear(const float *in, float *out, int planes, int h, int w, int H, int W, hipStream_t s) {
+extern "C" int dt_resize_bilinear(const float *in, float *out, int planes, int h, int w, int H, int W, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (!in || !out) return DT_E_NULL;
   if (planes < 1 || h < 1 || w < 1 || H < 1 || W < 1) return DT_E_SHAPE;
   const size_t total = (size_t)planes * H * ((W + 3) / 4);

@@ -71,7 +71,8 @@ __global__ __launch_bounds__(256) void traj_metrics_kernel(const float *__restri
   }
 }
 
-int launch_traj_metrics(const float *X, const float *Y, int nT, int nS, int B, int E, double *out, hipStream_t s) {
+extern "C" int dt_traj_metrics(const float *X, const float *Y, int nT, int nS, int B, int E, double *out, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (!X || !Y || !out) return DT_E_NULL;
   if (nT < 1 || nS < 1 || B < 1 || E < 4 || E % 4) return DT_E_SHAPE;
   const int n_max = nT > nS ? nT : nS;
@@ -115,7 +116,8 @@ __global__ __launch_bounds__(256) void pair_stats_kernel(const float *__restrict
   }
 }
 
-int launch_pair_stats(const float *X, const float *Y, int n, int B, int E, double *out, hipStream_t s) {
+extern "C" int dt_pair_stats(const float *X, const float *Y, int n, int B, int E, double *out, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (!X || !Y || !out) return DT_E_NULL;
   if (n < 1 || B < 1 || E < 4 || E % 4 || n > 65535) return DT_E_SHAPE;
   ProfileScope prof(KC_METRICS, 0.0, 8.0 * B * E * (double)n, s);
@@ -137,7 +139,8 @@ __global__ __launch_bounds__(256) void sample_mean_kernel(const float *__restric
   }
 }
 
-int launch_sample_mean(const float *traj, int n, int B, int E, float *out, hipStream_t s) {
+extern "C" int dt_traj_sample_mean(const float *traj, int n, int B, int E, float *out, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (!traj || !out) return DT_E_NULL;
   if (n < 1 || B < 1 || E < 1) return DT_E_SHAPE;
   const size_t total = (size_t)n * E;
@@ -197,8 +200,9 @@ __global__ __launch_bounds__(256) void wasserstein_kernel(const float *__restric
   if (threadIdx.x == 0) out[(size_t)b * n + i] = acc[0] / (double)cnt;
 }
 
-int launch_wasserstein(const float *X, const float *Y, int n, int B, int E, const int32_t *index,
-                       const int32_t *index_row, int n_idx, double *out, hipStream_t s) {
+extern "C" int dt_traj_wasserstein(const float *X, const float *Y, int n, int B, int E, const int32_t *index,
+                                   const int32_t *index_row, int n_idx, double *out, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (!X || !Y || !out) return DT_E_NULL;
   const int cnt = index ? n_idx : E;
   if (n < 1 || B < 1 || cnt < 1 || cnt > 4096 || n > 65535) return DT_E_SHAPE;
@@ -331,7 +335,8 @@ __global__ __launch_bounds__(256) void pair_metrics_kernel(const float *__restri
   }
 }
 
-int launch_pair_metrics(const float *X, const float *Y, int n, int B, int E, double *out_sums, double *out_w1, hipStream_t s) {
+extern "C" int dt_traj_pair_metrics(const float *X, const float *Y, int n, int B, int E, double *out_sums, double *out_w1, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (!X || !Y || !out_sums || !out_w1) return DT_E_NULL;
   if (n < 1 || B < 1 || E < 4 || E % 4 || E > 4096 || n > 65535 || B > 65535) return DT_E_SHAPE;
   // algorithmic bytes: one read of both trajectories (2 (T+1) E 4 per pair)
@@ -379,8 +384,9 @@ __global__ __launch_bounds__(256) void resampled_distance_kernel(const float *__
   if (threadIdx.x == 0) out[(size_t)b * n_short + i] = sqrt(acc[0]);
 }
 
-int launch_resampled_distance(const float *L, const float *S, int n_long, int n_short, int B, int E, double *out,
-                              hipStream_t s) {
+extern "C" int dt_traj_resampled_distance(const float *L, const float *S, int n_long, int n_short, int B, int E, double *out,
+                                          void *stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (!L || !S || !out) return DT_E_NULL;
   if (n_long < 2 || n_short < 1 || n_short > n_long || B < 1 || E < 1 || n_short > 65535) return DT_E_SHAPE;
   ProfileScope prof(KC_RESAMPLE, 0.0, 12.0 * B * E * (double)n_short, s);

@@ -18,26 +18,6 @@
 
 #include "dt_fused.h"
 #include "dt_internal.h"
-#include "../../include/dt_hip_noise.h"
-
-namespace dt {
-int launch_cfg_update(int rule, const float *x, const float *eu, const float *ec, const float *z,
-                      const int32_t *z_row, long long z_shift, const float coef[4], int has_noise, const float *w,
-                      float w_scalar, float *out, int B, int E, hipStream_t s);
-int launch_cfg_update_lowres(int rule, const float *x, const float *lowres_u, const float *lowres_c, const float *z,
-                             const int32_t *z_row, long long z_shift, const float coef[4], int has_noise, const float *w,
-                             float w_scalar, float *out, int B, int C, int H, int W, int b_single, hipStream_t s);
-int launch_traj_metrics(const float *X, const float *Y, int nT, int nS, int B, int E, double *out, hipStream_t s);
-int launch_wasserstein(const float *X, const float *Y, int n, int B, int E, const int32_t *index,
-                       const int32_t *index_row, int n_idx, double *out, hipStream_t s);
-int launch_resampled_distance(const float *L, const float *S, int n_long, int n_short, int B, int E, double *out,
-                              hipStream_t s);
-int launch_pair_metrics(const float *X, const float *Y, int n, int B, int E, double *out_sums, double *out_w1, hipStream_t s);
-int launch_pair_stats(const float *X, const float *Y, int n, int B, int E, double *out, hipStream_t s);
-int launch_sample_mean(const float *traj, int n, int B, int E, float *out, hipStream_t s);
-int launch_resize_bilinear(const float *in, float *out, int planes, int h, int w, int H, int W, hipStream_t s);
-int launch_q_sample(const float *x0, const float *z, const float *coef, int n_groups, int B, int E, float *out, hipStream_t s);
-}  // namespace dt
 
 using namespace dt;
 
@@ -111,11 +91,25 @@ struct BlockW {
   int tb_off;             // channel offset of this block in a time-bias row
 };
 
+// One forward shape, the key of every launch plan: Bt batch rows of H x W pictures made of imgs images -- every image once
+// (pass 0), then the images from `single` on a second time (pass 1), or all of them Bt / imgs times when single == 0.  The
+// split is part of the key because enc1's launches run over the images, not the rows.
+struct FwdShape {
+  int Bt, H, W, imgs, single;
+  static FwdShape rows_only(int Bt, int H, int W) { return FwdShape{Bt, H, W, Bt, 0}; }   // for what the split does not change (the workspace layout)
+  bool operator==(const FwdShape &o) const { return Bt == o.Bt && H == o.H && W == o.W && imgs == o.imgs && single == o.single; }
+  // DT_OK, DT_E_SHAPE (rows, images or picture size the kernels do not run) or DT_E_ARG (rows and images that do not fit together)
+  int validate() const {
+    if (Bt < 1 || imgs < 1 || H < 16 || W < 16 || H % 16 || W % 16) return DT_E_SHAPE;
+    if (single < 0 || single >= imgs || (single ? Bt != 2 * imgs - single : Bt % imgs != 0)) return DT_E_ARG;
+    return DT_OK;
+  }
+};
+
 // (tile, split) choice of the three conv slots (0 = 1x1 skip, 1 = conv1, 2 = conv2) of every block for
 // one forward shape, filled in by dt_unet_autotune; absent shapes use heuristic_choice
 struct TunedShape {
-  int Bt, H, W;
-  int imgs, single;   // how the Bt rows split into images (see ShapeInfo): enc1's launches run over the images
+  FwdShape shape;
   ConvChoice c[kBlocks][3];
 };
 
@@ -126,14 +120,8 @@ struct LoopGraph {
   hipGraph_t graph;
 };
 
-// how a forward shape (Bt rows) splits into images: recorded by every forward so that the tuning / reporting hooks, which are
-// keyed by the row count alone, describe the launches the forward really issues (enc1 runs over the images, not the rows)
-struct ShapeInfo { int Bt, H, W, imgs, single; };
-
 struct dt_unet {
   std::vector<TunedShape> tuned;
-  mutable std::vector<ShapeInfo> shapes;
-  mutable std::mutex shape_mu;
   // replay cache of the sampler loop (not part of the handle's logical state, hence mutable + its own lock: the
   // sampler may be entered from several host threads); dropped whenever the launch plan changes
   mutable std::vector<LoopGraph> graphs;
@@ -187,7 +175,8 @@ struct Plan {
 // level (power-of-two divisor of the image size) of the 8 blocks
 const int kDiv[kBlocks] = {1, 2, 4, 8, 16, 8, 4, 2};
 
-Plan make_plan(const dt_unet *u, int Bt, int H, int W) {
+Plan make_plan(const dt_unet *u, const FwdShape &sh) {
+  const int Bt = sh.Bt, H = sh.H, W = sh.W;
   Plan p{};
   Bump b;
   size_t slab = 0;
@@ -217,34 +206,16 @@ void drop_graphs(dt_unet *u) {
   u->graphs.clear();
 }
 
-const TunedShape *find_tuned(const dt_unet *u, int Bt, int H, int W, int imgs, int single) {
+const TunedShape *find_tuned(const dt_unet *u, const FwdShape &sh) {
   for (const TunedShape &t : u->tuned)
-    if (t.Bt == Bt && t.H == H && t.W == W && t.imgs == imgs && t.single == single) return &t;
+    if (t.shape == sh) return &t;
   return nullptr;
-}
-
-void shape_images(const dt_unet *u, int Bt, int H, int W, int &imgs, int &single) {
-  {
-    std::lock_guard<std::mutex> lock(u->shape_mu);
-    for (const ShapeInfo &si : u->shapes)
-      if (si.Bt == Bt && si.H == H && si.W == W) { imgs = si.imgs; single = si.single; return; }
-  }
-  imgs = Bt % 2 == 0 ? Bt / 2 : Bt;   // never run yet: the sampler's two-pass CFG shape
-  single = 0;
-}
-
-void note_shape(const dt_unet *u, int Bt, int H, int W, int imgs, int single) {
-  std::lock_guard<std::mutex> lock(u->shape_mu);
-  for (ShapeInfo &si : u->shapes)
-    if (si.Bt == Bt && si.H == H && si.W == W) { si.imgs = imgs; si.single = single; return; }
-  u->shapes.push_back(ShapeInfo{Bt, H, W, imgs, single});
 }
 
 // The launches of one forward shape, resolved once and free of pointers: the choice of every convolution slot (0 = 1x1 skip,
 // 1 = conv1, 2 = conv2) of every block and the per-block facts that follow from them.  bind_conv() binds one slot to buffers.
-// imgs images make up the Bt rows: every image once (pass 0), then the images from `single` on a second time (pass 1).
 struct ResolvedForward {
-  int Bt, H, W, imgs, single;
+  FwdShape shape;
   bool shared_enc1;                 // enc1 runs once over the images for all passes (its conv2 writes every pass)
   ConvChoice c[kBlocks][3];         // c[j][2].fuse: conv2 folds the block's 1x1 skip in (slot 0 does not launch)
   bool pool_fused[kBlocks];         // enc1..enc4: conv2's epilogue writes the 2x2 max pool
@@ -258,22 +229,22 @@ bool has_launch(const dt_unet *u, int j, int slot) { return slot == 2 || (j > 0 
 
 ConvLayer conv_layer(const dt_unet *u, const ResolvedForward &f, int j, int slot) {
   const BlockW &k = u->blk[j];
-  const int h = f.H / kDiv[j], w = f.W / kDiv[j];
-  const int M = (j == 0 && f.shared_enc1 ? f.imgs : f.Bt) * h * w;
+  const int h = f.shape.H / kDiv[j], w = f.shape.W / kDiv[j];
+  const int M = (j == 0 && f.shared_enc1 ? f.shape.imgs : f.shape.Bt) * h * w;
   const int taps = slot == 0 || (h == 1 && w == 1) ? 1 : 9;   // a 1x1 image only ever sees the centre tap of a padded 3x3 kernel
   return ConvLayer{M, w, k.n_p, slot == 2 ? k.cout_p : k.cin_p, taps, j > 0 && M <= kSplitMaxRows, slot == 2 && j > 0 && k.has_res};
 }
 
-ResolvedForward resolve_forward(const dt_unet *u, int Bt, int H, int W, int imgs, int single, const TunedShape *tuned) {
+ResolvedForward resolve_forward(const dt_unet *u, const FwdShape &sh, const TunedShape *tuned) {
   ResolvedForward f{};
-  f.Bt = Bt; f.H = H; f.W = W; f.imgs = imgs; f.single = single;
-  f.shared_enc1 = u->share_enc1 && (Bt + single) % imgs == 0;
+  f.shape = sh;
+  f.shared_enc1 = u->share_enc1 && (sh.Bt + sh.single) % sh.imgs == 0;
   for (int j = 0; j < kBlocks; ++j)
     for (int slot = 0; slot < 3; ++slot)
       if (has_launch(u, j, slot)) f.c[j][slot] = resolve_conv_choice(conv_layer(u, f, j, slot), tuned ? &tuned->c[j][slot] : nullptr, u->precision);
   for (int j = 0; j < kBlocks; ++j) {
     const ConvChoice &c2 = f.c[j][2];
-    const int h = H / kDiv[j], w = W / kDiv[j];
+    const int h = sh.H / kDiv[j], w = sh.W / kDiv[j];
     // encoder blocks enc1..enc4 feed a 2x2 max pool: folded into conv2's staged epilogue where a 32-row tile holds whole row
     // pairs (W a power of two <= 16); split launches pool in their slab-summing epilogue kernel instead
     f.pool_fused[j] = j <= 3 && h % 2 == 0 && w % 2 == 0 && (c2.splits > 1 || (w <= 16 && (w & (w - 1)) == 0));
@@ -314,9 +285,9 @@ ConvParams bind_conv(const dt_unet *u, const ResolvedForward &f, int j, int slot
     if (f.pool_fused[j]) p.pool_out = ws + pl.pool[j];
     if (j == 0) {
       // the C-channel skip of enc1 is recomputed in the epilogue from the patches' centre taps (k = 9c+4)
-      p.x3 = in; p.w3 = k.w3; p.x3_hw = h * w; p.x3_imgs = f.imgs; p.x3_c = u->desc.channels;
+      p.x3 = in; p.w3 = k.w3; p.x3_hw = h * w; p.x3_imgs = f.shape.imgs; p.x3_c = u->desc.channels;
       if (f.shared_enc1) {   // one launch over the images for all their passes
-        p.n_dup = (f.Bt + f.single) / f.imgs; p.dup_rows = p.M; p.dup_skip = f.single * h * w; p.tbc = tb + u->tb_cols;
+        p.n_dup = (f.shape.Bt + f.shape.single) / f.shape.imgs; p.dup_rows = p.M; p.dup_skip = f.shape.single * h * w; p.tbc = tb + u->tb_cols;
         p.skip_out = u->head_fusion && p.pool_out ? 1 : 0;   // only the pool reads enc1's output (else a pooling launch does)
       }
     } else {
@@ -344,10 +315,10 @@ int run_block(const dt_unet *u, const ResolvedForward &f, int j, const float *in
               int tb_div, hipStream_t s) {
   if (j == 0) {
     const BlockW &k = u->blk[0];
-    if (!f.shared_enc1 && f.single) return DT_E_ARG;   // mixed batches exist in the shared-enc1 formulation only
+    if (!f.shared_enc1 && f.shape.single) return DT_E_ARG;   // mixed batches exist in the shared-enc1 formulation only
     // (shared: the passes' time biases enter in conv2's epilogue)
     const int st = launch_first_conv(in, k.w1, k.s1, k.h1, f.shared_enc1 ? nullptr : tb + k.tb_off, u->tb_stride, tb_div, ws + pl.h[0],
-                                     f.imgs, f.shared_enc1 ? 1 : f.Bt / f.imgs, u->desc.channels, pl.H[0], pl.W[0], k.cout, k.cout_p, s);
+                                     f.shape.imgs, f.shared_enc1 ? 1 : f.shape.Bt / f.shape.imgs, u->desc.channels, pl.H[0], pl.W[0], k.cout, k.cout_p, s);
     if (st) return st;
   }
   for (int slot = 0; slot < 3; ++slot) {
@@ -371,11 +342,11 @@ int run_block(const dt_unet *u, const ResolvedForward &f, int j, const float *in
 int forward_impl(const dt_unet *u, const float *x, int B, int n_pass, int H, int W, const float *tb, int tb_div,
                  float *eps, float *ws, size_t ws_bytes, hipStream_t s, int B_single = 0) {
   if (!u || !x || !tb || !ws) return DT_E_NULL;
-  if (B < 1 || n_pass < 1 || tb_div < 1 || H < 16 || W < 16 || H % 16 || W % 16) return DT_E_SHAPE;
-  if (B_single < 0 || B_single >= B || (B_single && n_pass != 2)) return DT_E_ARG;
+  if (n_pass < 1 || tb_div < 1) return DT_E_SHAPE;
   const int Bt = B * n_pass - B_single * (n_pass - 1);
-  note_shape(u, Bt, H, W, B, B_single);
-  const Plan pl = make_plan(u, Bt, H, W);
+  const FwdShape sh{Bt, H, W, B, B_single};
+  if (const int bad = sh.validate()) return bad;
+  const Plan pl = make_plan(u, sh);
   if (pl.total * sizeof(float) > ws_bytes) return DT_E_WORKSPACE;
   if (use_fused(u, H, W) && eps) {           // small model: the whole forward is one launch (dt_fused.hip)
     if (Bt % tb_div) return DT_E_ARG;
@@ -384,7 +355,7 @@ int forward_impl(const dt_unet *u, const float *x, int B, int n_pass, int H, int
     a.mode = FUSED_FORWARD; a.x = x; a.eps = eps;
     return launch_unet_fused(a, s);
   }
-  const ResolvedForward f = resolve_forward(u, Bt, H, W, B, B_single, find_tuned(u, Bt, H, W, B, B_single));
+  const ResolvedForward f = resolve_forward(u, sh, find_tuned(u, sh));
   int st = DT_OK;
   const float *cur = x;                     // enc1 reads the NCHW image itself (first-layer kernel, skip in conv2's epilogue)
   for (int j = 0; j < kBlocks; ++j) {
@@ -412,9 +383,6 @@ int forward_impl(const dt_unet *u, const float *x, int B, int n_pass, int H, int
   if (!eps) return DT_OK;                  // the sampler's fused update interpolates the low-resolution output itself
   return launch_head_upsample(ws + pl.lowres, eps, Bt, pl.H[7], pl.W[7], u->desc.channels, s);
 }
-
-// float offset of the low-resolution head output [Bt][H/2][W/2][4] inside the workspace
-size_t lowres_offset(const dt_unet *u, int Bt, int H, int W) { return make_plan(u, Bt, H, W).lowres; }
 
 
 // ---- the fused small-model path (dt_fused.hip): packs + layer table at create time, one launch per forward / sampler call
@@ -500,6 +468,39 @@ void fused_common(const dt_unet *u, FusedArgs &a, int B, int n_pass, int B_singl
   a.tb_rows = (B * n_pass - B_single * (n_pass - 1)) / tb_div;
   a.flops_per_row = fused_flops_per_row(a.C, u->desc.dims[0], u->desc.dims[1]);
 }
+
+// HIP-event timing of one convolution launch for the autotuner and dt_unet_time_conv (synchronises the stream)
+struct ConvTimer {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  ~ConvTimer() {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+  int create() {
+    DT_HIP_TRY(hipEventCreate(&e0));
+    DT_HIP_TRY(hipEventCreate(&e1));
+    return DT_OK;
+  }
+  // *ms: average milliseconds of `reps` back-to-back launches of q after one warm launch: in the sampler launches queue
+  // behind each other, so a launch is not charged the idle-queue launch latency per kernel (which would bias against
+  // split launches = two kernels).  Returns the status of the launches.
+  int time(const ConvParams &q, int reps, hipStream_t s, float *ms) {
+    *ms = 0.f;
+    int st = launch_conv(q, s);
+    if (st != DT_OK) return st;
+    (void)hipEventRecord(e0, s);
+    for (int rep = 0; rep < reps && st == DT_OK; ++rep) st = launch_conv(q, s);
+    (void)hipEventRecord(e1, s);
+    if (hipEventSynchronize(e1) != hipSuccess) st = (int)hipGetLastError();
+    if (st != DT_OK) return st;
+    (void)hipEventElapsedTime(ms, e0, e1);
+    *ms /= reps;
+    return DT_OK;
+  }
+};
+
+// the caller's checks of a (block, slot) pair of the plan hooks
+bool slot_exists(int block, int slot) { return block >= 0 && block < kBlocks && slot >= 0 && slot <= 2; }
 }  // namespace
 
 extern "C" {
@@ -654,8 +655,9 @@ int dt_unet_time_bias(const dt_unet *h, const int32_t *t, const float *cond, con
 }
 
 size_t dt_unet_workspace_bytes(const dt_unet *h, int batch_total, int H, int W) {
-  if (!h || batch_total < 1 || H < 16 || W < 16 || H % 16 || W % 16) return 0;
-  return make_plan(h, batch_total, H, W).total * sizeof(float);
+  const FwdShape sh = FwdShape::rows_only(batch_total, H, W);
+  if (!h || sh.validate() != DT_OK) return 0;
+  return make_plan(h, sh).total * sizeof(float);
 }
 
 int dt_unet_forward(const dt_unet *h, const float *x, int B, int n_pass, int H, int W, const float *tb, int tb_div,
@@ -672,19 +674,18 @@ constexpr float kSplitMargin = 1.05f;
 // `stream` (synchronises; call it outside hot loops and graph captures) and records the fastest.
 // Activations in the workspace are whatever the last forward left there (run one first: all-zero or
 // garbage operands would let the chip clock differently from real data).
-int dt_unet_autotune(dt_unet *h, int batch_total, int H, int W, void *workspace, size_t ws_bytes, void *stream) {
+int dt_unet_autotune(dt_unet *h, int batch_total, int H, int W, int images, int single, void *workspace, size_t ws_bytes,
+                     void *stream) {
   if (!h || !workspace) return DT_E_NULL;
-  if (batch_total < 1 || H < 16 || W < 16 || H % 16 || W % 16) return DT_E_SHAPE;
+  TunedShape t{{batch_total, H, W, images, single}, {}};
+  if (const int bad = t.shape.validate()) return bad;
   hipStream_t s = (hipStream_t)stream;
-  const Plan pl = make_plan(h, batch_total, H, W);
+  const Plan pl = make_plan(h, t.shape);
   if (pl.total * sizeof(float) > ws_bytes) return DT_E_WORKSPACE;
   float *ws = (float *)workspace;
-  hipEvent_t e0, e1;
-  DT_HIP_TRY(hipEventCreate(&e0));
-  DT_HIP_TRY(hipEventCreate(&e1));
-  TunedShape t{batch_total, H, W, 0, 0, {}};
-  shape_images(h, batch_total, H, W, t.imgs, t.single);   // the split of the last forward with this row count
-  const ResolvedForward f = resolve_forward(h, batch_total, H, W, t.imgs, t.single, nullptr);   // candidates start from the defaults
+  ConvTimer timer;
+  if (const int bad = timer.create()) return bad;
+  const ResolvedForward f = resolve_forward(h, t.shape, nullptr);   // candidates start from the defaults
   const float *tb = h->slab;   // any readable floats: only timing matters here
   int st = DT_OK;
   {   // The clocks of an idle GPU take tens of milliseconds of load to settle (the same launch measures 15 % slower
@@ -702,21 +703,12 @@ int dt_unet_autotune(dt_unet *h, int batch_total, int H, int W, void *workspace,
       best.fuse = 0;               // candidates start from the UNFUSED launch (the default may have folded the skip in)
       const ConvLayer L = conv_layer(h, f, j, slot);
       float best_ms = 1e30f;
-      // average milliseconds of `reps` back-to-back launches of one candidate (one warm launch first): in the sampler
-      // launches queue behind each other, so a candidate is not charged the idle-queue launch latency per kernel
-      // (which would bias against split launches = two kernels); < 0: the launch cannot run here
+      // the timed average of one candidate; < 0: the launch cannot run here
       auto measure = [&](const ConvParams &q, int reps) -> float {
-        int lst = launch_conv(q, s);
-        if (lst == DT_E_SHAPE || lst == DT_E_ARG) return -1.f;
-        if (lst != DT_OK) { st = lst; return -1.f; }
-        (void)hipEventRecord(e0, s);
-        for (int rep = 0; rep < reps && lst == DT_OK; ++rep) lst = launch_conv(q, s);
-        (void)hipEventRecord(e1, s);
-        if (hipEventSynchronize(e1) != hipSuccess) lst = (int)hipGetLastError();
-        if (lst != DT_OK) { st = lst; return -1.f; }
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        return ms / reps;
+        float ms;
+        const int lst = timer.time(q, reps, s, &ms);
+        if (lst != DT_OK && lst != DT_E_SHAPE && lst != DT_E_ARG) st = lst;
+        return lst == DT_OK ? ms : -1.f;
       };
       struct Cand { ConvChoice c; ConvParams q; float cost; };
       std::vector<Cand> cands;
@@ -772,10 +764,8 @@ int dt_unet_autotune(dt_unet *h, int batch_total, int H, int W, void *workspace,
       if (slot == 0) skip_ms = best_ms;
     }
   }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   if (st != DT_OK) return st;
-  TunedShape *old = const_cast<TunedShape *>(find_tuned(h, t.Bt, t.H, t.W, t.imgs, t.single));
+  TunedShape *old = const_cast<TunedShape *>(find_tuned(h, t.shape));
   if (old) *old = t;
   else h->tuned.push_back(t);
   drop_graphs(h);
@@ -784,37 +774,26 @@ int dt_unet_autotune(dt_unet *h, int batch_total, int H, int W, void *workspace,
 
 /* tuning / profiling aid: average milliseconds (HIP events, synchronises) of ONE convolution launch of a
  * forward shape under an explicit (tile, split, arithmetic, fuse) choice, plus its algorithmic FLOPs */
-int dt_unet_time_conv(const dt_unet *h, int batch_total, int H, int W, int block, int slot, int bm, int bn, int splits,
-                      int prec, int fuse, int reps, void *workspace, size_t ws_bytes, void *stream, float *ms,
-                      double *flops) {
+int dt_unet_time_conv(const dt_unet *h, int batch_total, int H, int W, int images, int single, int block, int slot, int bm,
+                      int bn, int splits, int prec, int fuse, int reps, void *workspace, size_t ws_bytes, void *stream,
+                      float *ms, double *flops) {
   if (!h || !workspace || !ms || !flops) return DT_E_NULL;
-  if (block < 0 || block >= kBlocks || slot < 0 || slot > 2 || reps < 1) return DT_E_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  const Plan pl = make_plan(h, batch_total, H, W);
+  if (!slot_exists(block, slot) || reps < 1) return DT_E_ARG;
+  TunedShape req{{batch_total, H, W, images, single}, {}};
+  if (const int bad = req.shape.validate()) return bad;
+  const Plan pl = make_plan(h, req.shape);
   if (pl.total * sizeof(float) > ws_bytes) return DT_E_WORKSPACE;
   float *ws = (float *)workspace;
   const float *in = block == 0 ? ws + pl.h[0] : (block <= 4 ? ws + pl.pool[block - 1] : ws + pl.cat[block - 5]);
   if (!has_launch(h, block, slot)) { *ms = 0.f; *flops = 0.0; return DT_OK; }
-  TunedShape req{};   // every slot asks for the choice: (block, slot) is bound with what follows from its own resolution only
+  // every slot asks for the choice: (block, slot) is bound with what follows from its own resolution only
   std::fill_n(&req.c[0][0], kBlocks * 3, ConvChoice{bm, bn, splits, prec, fuse});
-  shape_images(h, batch_total, H, W, req.imgs, req.single);
-  const ResolvedForward f = resolve_forward(h, batch_total, H, W, req.imgs, req.single, &req);
-  ConvParams p = bind_conv(h, f, block, slot, f.c[block][slot], in, ws, pl, h->slab, batch_total);
+  const ResolvedForward f = resolve_forward(h, req.shape, &req);
+  const ConvParams p = bind_conv(h, f, block, slot, f.c[block][slot], in, ws, pl, h->slab, batch_total);
   *flops = 2.0 * p.M * (double)p.cout_real * ((double)p.cin_real * p.ksize * p.ksize + (p.in2 ? p.cin2_real : 0));
-  hipEvent_t e0, e1;
-  DT_HIP_TRY(hipEventCreate(&e0));
-  DT_HIP_TRY(hipEventCreate(&e1));
-  int st = launch_conv(p, s);   // warm
-  (void)hipEventRecord(e0, s);
-  for (int r = 0; r < reps && st == DT_OK; ++r) st = launch_conv(p, s);
-  (void)hipEventRecord(e1, s);
-  if (hipEventSynchronize(e1) != hipSuccess) st = (int)hipGetLastError();
-  float t = 0.f;
-  (void)hipEventElapsedTime(&t, e0, e1);
-  *ms = t / reps;
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  return st;
+  ConvTimer timer;
+  if (const int bad = timer.create()) return bad;
+  return timer.time(p, reps, (hipStream_t)stream, ms);
 }
 
 int dt_unet_set_precision(dt_unet *h, int precision) {
@@ -846,42 +825,32 @@ int dt_unet_fused_active(const dt_unet *h, int H, int W) {
 }
 
 /* test / report hook: the (bm, bn, splits) in use for block j, slot (0 skip, 1 conv1, 2 conv2) at a shape */
-int dt_unet_conv_choice(const dt_unet *h, int batch_total, int H, int W, int block, int slot, int *bm, int *bn,
-                        int *splits, int *prec, int *tuned) {
+int dt_unet_conv_choice(const dt_unet *h, int batch_total, int H, int W, int images, int single, int block, int slot, int *bm,
+                        int *bn, int *splits, int *prec, int *tuned) {
   if (!h || !bm || !bn || !splits || !prec || !tuned) return DT_E_NULL;
-  if (block < 0 || block >= kBlocks || slot < 0 || slot > 2 || H % 16 || W % 16 || batch_total < 1) return DT_E_ARG;
-  int imgs = 0, single = 0;
-  shape_images(h, batch_total, H, W, imgs, single);
-  const TunedShape *t = find_tuned(h, batch_total, H, W, imgs, single);
-  const ResolvedForward f = resolve_forward(h, batch_total, H, W, imgs, single, t);
+  if (!slot_exists(block, slot)) return DT_E_ARG;
+  const FwdShape sh{batch_total, H, W, images, single};
+  if (const int bad = sh.validate()) return bad;
+  const TunedShape *t = find_tuned(h, sh);
+  const ResolvedForward f = resolve_forward(h, sh, t);
   const ConvChoice &c = f.c[block][slot];   // (all zero where the slot has no launch of its own)
   *bm = c.bm; *bn = c.bn; *splits = c.splits; *prec = c.kind + (c.fuse ? 8 : 0); *tuned = t && has_launch(h, block, slot);
   if (slot == 0 && f.c[block][2].fuse) *bm = *bn = *splits = 0;   // folded into conv2
   return DT_OK;
 }
 
-int dt_unet_declare_shape(dt_unet *h, int batch_total, int H, int W, int images, int single) {
+int dt_unet_set_conv_choice(dt_unet *h, int batch_total, int H, int W, int images, int single, int block, int slot, int bm,
+                            int bn, int splits, int prec, int fuse) {
   if (!h) return DT_E_NULL;
-  if (batch_total < 1 || H < 16 || W < 16 || H % 16 || W % 16 || images < 1 || single < 0 || single >= images) return DT_E_ARG;
-  if (batch_total != images && batch_total != 2 * images - single && (single || batch_total % images)) return DT_E_ARG;
-  note_shape(h, batch_total, H, W, images, single);
-  return DT_OK;
-}
-
-int dt_unet_set_conv_choice(dt_unet *h, int batch_total, int H, int W, int block, int slot, int bm, int bn, int splits,
-                            int prec, int fuse) {
-  if (!h) return DT_E_NULL;
-  if (block < 0 || block >= kBlocks || slot < 0 || slot > 2 || H < 16 || W < 16 || H % 16 || W % 16 || batch_total < 1)
-    return DT_E_ARG;
+  if (!slot_exists(block, slot)) return DT_E_ARG;
+  const FwdShape sh{batch_total, H, W, images, single};
+  if (const int bad = sh.validate()) return bad;
   const ConvChoice c{bm, bn, splits, prec, fuse};
   if (!conv_choice_valid(c, slot, h->blk[block].n_p)) return DT_E_ARG;
-  int imgs = 0, single = 0;
-  shape_images(h, batch_total, H, W, imgs, single);
-  TunedShape *t = const_cast<TunedShape *>(find_tuned(h, batch_total, H, W, imgs, single));
+  TunedShape *t = const_cast<TunedShape *>(find_tuned(h, sh));
   if (!t) {   // start from what an untuned forward would launch
-    const ResolvedForward f = resolve_forward(h, batch_total, H, W, imgs, single, nullptr);
-    TunedShape fresh{batch_total, H, W, imgs, single, {}};
-    memcpy(fresh.c, f.c, sizeof(f.c));
+    TunedShape fresh{sh, {}};
+    memcpy(fresh.c, resolve_forward(h, sh, nullptr).c, sizeof(fresh.c));
     h->tuned.push_back(fresh);
     t = &h->tuned.back();
   }
@@ -893,64 +862,76 @@ int dt_unet_set_conv_choice(dt_unet *h, int batch_total, int H, int W, int block
 int dt_unet_debug_activation(const dt_unet *h, int batch_total, int H, int W, int which, size_t *off, int *cp,
                              int *oh, int *ow) {
   if (!h || !off || !cp || !oh || !ow) return DT_E_NULL;
-  if (which < 0 || which > kBlocks || batch_total < 1 || H % 16 || W % 16) return DT_E_ARG;
-  const Plan pl = make_plan(h, batch_total, H, W);
+  if (which < 0 || which > kBlocks) return DT_E_ARG;
+  const FwdShape sh = FwdShape::rows_only(batch_total, H, W);
+  if (const int bad = sh.validate()) return bad;
+  const Plan pl = make_plan(h, sh);
   if (which == kBlocks) { *off = pl.slab; *cp = 0; *oh = 0; *ow = 0; return DT_OK; }   // the split-K slab (diagnostics)
   *off = pl.o[which]; *cp = h->blk[which].cout_p; *oh = pl.H[which]; *ow = pl.W[which];
   return DT_OK;
 }
 
-int dt_cfg_update(int rule, const float *x, const float *eu, const float *ec, const float *z, const int32_t *z_row,
-                  const float coef[4], int has_noise, const float *w, float w_scalar, float *out, int B, int E,
-                  void *stream) {
-  return launch_cfg_update(rule, x, eu, ec, z, z_row, 0, coef, has_noise, w, w_scalar, out, B, E, (hipStream_t)stream);
-}
+// One sampler call.  tb_div rows of a step's forward share one time-bias row; B_single: see forward_impl.
+struct SampleArgs {
+  int rule, B, n_pass, B_single, H, W, n_steps;
+  const float *tb;
+  int tb_div;
+  const float *coef;
+  const int32_t *has_noise;
+  const float *z;
+  const int32_t *z_row;
+  const int64_t *z_shift;
+  const float *w;
+  float w_scalar;
+  float *traj;
+  void *ws;
+  size_t ws_bytes;
+  hipStream_t s;
+};
 
-// tb_div rows of a step's forward share one time-bias row (0: one row per pass, i.e. tb_div = B); B_single: see forward_impl
-static int sample_loop(const dt_unet *h, int rule, int B, int n_pass, int H, int W, int n_steps, const float *tb,
-                       const float *coef, const int32_t *has_noise, const float *z, const int32_t *z_row,
-                       const int64_t *z_shift, const float *w, float w_scalar, float *traj, float *eps_scratch,
-                       void *ws, size_t ws_bytes, hipStream_t s, int B_single = 0, int tb_div = 0) {
+static int sample_loop(const dt_unet *h, const SampleArgs &a) {
+  const int B = a.B, H = a.H, W = a.W;
   const int E = h->desc.channels * H * W;
   const size_t slot = (size_t)B * E;
-  const int Bt = B * n_pass - B_single * (n_pass - 1);
-  if (!tb_div) tb_div = B;
-  if (Bt % tb_div) return DT_E_ARG;
-  const int tb_rows = Bt / tb_div;         // time-bias rows per step
-  if (make_plan(h, Bt, H, W).total * sizeof(float) > ws_bytes) return DT_E_WORKSPACE;
+  const FwdShape sh{B * a.n_pass - a.B_single * (a.n_pass - 1), H, W, B, a.B_single};
+  if (const int bad = sh.validate()) return bad;
+  if (a.tb_div < 1 || sh.Bt % a.tb_div) return DT_E_ARG;
+  const int tb_rows = sh.Bt / a.tb_div;         // time-bias rows per step
+  const Plan pl = make_plan(h, sh);
+  if (pl.total * sizeof(float) > a.ws_bytes) return DT_E_WORKSPACE;
   if (use_fused(h, H, W)) {
     // small model: forward + CFG mix + update of up to kFusedMaxSteps timesteps per launch, images resident in LDS
-    for (int i0 = 0; i0 < n_steps; i0 += kFusedMaxSteps) {
-      const int n = n_steps - i0 < kFusedMaxSteps ? n_steps - i0 : kFusedMaxSteps;
-      FusedArgs a{};
-      fused_common(h, a, B, n_pass, B_single, tb + (size_t)i0 * tb_rows * h->tb_stride, tb_div);
-      a.mode = FUSED_LOOP; a.rule = rule; a.n_steps = n;
-      a.traj = traj + (size_t)i0 * slot; a.z = z; a.z_row = z_row; a.wg = w; a.w_scalar = w_scalar;
+    for (int i0 = 0; i0 < a.n_steps; i0 += kFusedMaxSteps) {
+      const int n = a.n_steps - i0 < kFusedMaxSteps ? a.n_steps - i0 : kFusedMaxSteps;
+      FusedArgs fa{};
+      fused_common(h, fa, B, a.n_pass, a.B_single, a.tb + (size_t)i0 * tb_rows * h->tb_stride, a.tb_div);
+      fa.mode = FUSED_LOOP; fa.rule = a.rule; fa.n_steps = n;
+      fa.traj = a.traj + (size_t)i0 * slot; fa.z = a.z; fa.z_row = a.z_row; fa.wg = a.w; fa.w_scalar = a.w_scalar;
       for (int i = 0; i < n; ++i) {
-        a.coef[i][0] = coef[4 * (i0 + i)]; a.coef[i][1] = coef[4 * (i0 + i) + 1]; a.coef[i][2] = coef[4 * (i0 + i) + 2];
-        a.z_shift[i] = z_shift ? (long long)z_shift[i0 + i] : 0;
-        if (has_noise[i0 + i]) a.noise_mask |= 1ull << i;
-        if (has_noise[i0 + i] && !z) return DT_E_NULL;
+        fa.coef[i][0] = a.coef[4 * (i0 + i)]; fa.coef[i][1] = a.coef[4 * (i0 + i) + 1]; fa.coef[i][2] = a.coef[4 * (i0 + i) + 2];
+        fa.z_shift[i] = a.z_shift ? (long long)a.z_shift[i0 + i] : 0;
+        if (a.has_noise[i0 + i]) fa.noise_mask |= 1ull << i;
+        if (a.has_noise[i0 + i] && !a.z) return DT_E_NULL;
       }
-      const int st = launch_unet_fused(a, s);
+      const int st = launch_unet_fused(fa, a.s);
       if (st) return st;
     }
     return DT_OK;
   }
-  const float *lowres = (const float *)ws + lowres_offset(h, Bt, H, W);
-  (void)eps_scratch;                       // kept in the ABI: callers still hand in the scratch the unfused path used
-  for (int i = 0; i < n_steps; ++i) {
-    const float *x = traj + (size_t)i * slot;
-    float *xn = traj + (size_t)(i + 1) * slot;
-    const bool dead = rule == DT_RULE_ENGINE && !has_noise[i];   // t == 0: the prediction is never used
+  const float *lowres = (const float *)a.ws + pl.lowres;   // the low-resolution head output [Bt][H/2][W/2][4]
+  for (int i = 0; i < a.n_steps; ++i) {
+    const float *x = a.traj + (size_t)i * slot;
+    float *xn = a.traj + (size_t)(i + 1) * slot;
+    const bool dead = a.rule == DT_RULE_ENGINE && !a.has_noise[i];   // t == 0: the prediction is never used
     if (!dead) {      // the forward stops at the low-resolution head output; the update interpolates it (no eps tensor)
-      int st = forward_impl(h, x, B, n_pass, H, W, tb + (size_t)i * tb_rows * h->tb_stride, tb_div, nullptr, (float *)ws, ws_bytes, s, B_single);
+      int st = forward_impl(h, x, B, a.n_pass, H, W, a.tb + (size_t)i * tb_rows * h->tb_stride, a.tb_div, nullptr, (float *)a.ws, a.ws_bytes,
+                            a.s, a.B_single);
       if (st) return st;
     }
     // second-pass rows start at row B and belong to images B_single .. B-1: indexed by image through a pointer shifted back
-    int st = launch_cfg_update_lowres(rule, x, lowres, n_pass == 2 ? lowres + (size_t)(B - B_single) * (H / 2) * (W / 2) * 4 : nullptr, z, z_row,
-                                      z_shift ? (long long)z_shift[i] : 0, coef + 4 * i, has_noise[i], w, w_scalar, xn, B,
-                                      h->desc.channels, H, W, B_single, s);
+    int st = launch_cfg_update_lowres(a.rule, x, lowres, a.n_pass == 2 ? lowres + (size_t)(B - a.B_single) * (H / 2) * (W / 2) * 4 : nullptr, a.z,
+                                      a.z_row, a.z_shift ? (long long)a.z_shift[i] : 0, a.coef + 4 * i, a.has_noise[i], a.w, a.w_scalar, xn,
+                                      B, h->desc.channels, H, W, a.B_single, a.s);
     if (st) return st;
   }
   return DT_OK;
@@ -963,24 +944,23 @@ static int sample_loop(const dt_unet *h, int rule, int B, int n_pass, int H, int
  * kernels (~6 us each at batch 8), not by host launch cost, which the host threads already hide. */
 int dt_sample_trajectory(const dt_unet *h, int rule, int B, int n_pass, int H, int W, int n_steps, const float *tb,
                          const float *coef, const int32_t *has_noise, const float *z, const int32_t *z_row,
-                         const int64_t *z_shift, const float *w, float w_scalar, float *traj, float *eps_scratch,
-                         void *ws, size_t ws_bytes, void *stream) {
-  if (!h || !tb || !coef || !has_noise || !traj || !ws) return DT_E_NULL;   // (eps_scratch is unused since the fused update: NULL is fine)
+                         const int64_t *z_shift, const float *w, float w_scalar, float *traj, void *ws, size_t ws_bytes,
+                         void *stream) {
+  if (!h || !tb || !coef || !has_noise || !traj || !ws) return DT_E_NULL;
   if (n_pass < 1 || n_pass > 2 || n_steps < 0 || rule < 0 || rule > DT_RULE_MANAGER) return DT_E_ARG;
   hipStream_t s = (hipStream_t)stream;
+  const SampleArgs a{rule, B, n_pass, 0, H, W, n_steps, tb, B, coef, has_noise, z, z_row, z_shift, w, w_scalar, traj, ws, ws_bytes, s};
   const char *genv = getenv("DT_GRAPH");
   const bool use_graph = genv && atoi(genv) != 0;
-  if (!use_graph || g_prof.on.load() || n_steps < 4)
-    return sample_loop(h, rule, B, n_pass, H, W, n_steps, tb, coef, has_noise, z, z_row, z_shift, w, w_scalar, traj,
-                       eps_scratch, ws, ws_bytes, s);
+  if (!use_graph || g_prof.on.load() || n_steps < 4) return sample_loop(h, a);
   // ---- key: every argument by value (the small host arrays by content)
   std::vector<unsigned char> key;
   auto put = [&key](const void *p, size_t n) { const unsigned char *c = (const unsigned char *)p; key.insert(key.end(), c, c + n); };
-  const int ints[7] = {rule, B, n_pass, H, W, n_steps, z_shift ? 1 : 0};
-  const void *ptrs[8] = {tb, z, z_row, w, traj, eps_scratch, ws, (const void *)s};
-  put(ints, sizeof(ints)); put(ptrs, sizeof(ptrs)); put(&w_scalar, sizeof(w_scalar)); put(&ws_bytes, sizeof(ws_bytes));
-  put(coef, sizeof(float) * 4 * n_steps); put(has_noise, sizeof(int32_t) * n_steps);
-  if (z_shift) put(z_shift, sizeof(int64_t) * n_steps);
+  const int ints[7] = {a.rule, a.B, a.n_pass, a.H, a.W, a.n_steps, a.z_shift ? 1 : 0};
+  const void *ptrs[7] = {a.tb, a.z, a.z_row, a.w, a.traj, a.ws, (const void *)a.s};
+  put(ints, sizeof(ints)); put(ptrs, sizeof(ptrs)); put(&a.w_scalar, sizeof(a.w_scalar)); put(&a.ws_bytes, sizeof(a.ws_bytes));
+  put(a.coef, sizeof(float) * 4 * n_steps); put(a.has_noise, sizeof(int32_t) * n_steps);
+  if (a.z_shift) put(a.z_shift, sizeof(int64_t) * n_steps);
   const dt_unet *hm = h;
   std::lock_guard<std::mutex> lock(hm->graph_mu);
   for (const LoopGraph &g : hm->graphs)
@@ -989,11 +969,9 @@ int dt_sample_trajectory(const dt_unet *h, int rule, int B, int n_pass, int H, i
   hipError_t e = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
   if (e != hipSuccess) {   // stream cannot be captured (e.g. the legacy default stream): plain launches
     (void)hipGetLastError();
-    return sample_loop(h, rule, B, n_pass, H, W, n_steps, tb, coef, has_noise, z, z_row, z_shift, w, w_scalar, traj,
-                       eps_scratch, ws, ws_bytes, s);
+    return sample_loop(h, a);
   }
-  const int st = sample_loop(h, rule, B, n_pass, H, W, n_steps, tb, coef, has_noise, z, z_row, z_shift, w, w_scalar, traj,
-                             eps_scratch, ws, ws_bytes, s);
+  const int st = sample_loop(h, a);
   LoopGraph g{};
   e = hipStreamEndCapture(s, &g.graph);
   if (st != DT_OK) { if (e == hipSuccess && g.graph) (void)hipGraphDestroy(g.graph); return st; }
@@ -1013,8 +991,8 @@ int dt_sample_trajectory_mixed(const dt_unet *h, int rule, int B, int B_single, 
   if (!h || !tb || !coef || !has_noise || !traj || !ws || !w) return DT_E_NULL;
   if (n_steps < 0 || rule < 0 || rule > DT_RULE_MANAGER || B < 2 || B_single < 1 || B_single >= B || tb_div < 1) return DT_E_ARG;
   if ((2 * B - B_single) % tb_div || B_single % tb_div || !h->share_enc1) return DT_E_ARG;   // a time-bias row never straddles the single / CFG boundary
-  return sample_loop(h, rule, B, 2, H, W, n_steps, tb, coef, has_noise, z, z_row, z_shift, w, 1.f, traj, nullptr, ws, ws_bytes,
-                     (hipStream_t)stream, B_single, tb_div);
+  return sample_loop(h, SampleArgs{rule, B, 2, B_single, H, W, n_steps, tb, tb_div, coef, has_noise, z, z_row, z_shift, w, 1.f, traj, ws, ws_bytes,
+                                   (hipStream_t)stream});
 }
 
 int dt_unet_forward_mixed(const dt_unet *h, const float *x, int B, int B_single, int H, int W, const float *tb, int tb_div,
@@ -1062,40 +1040,6 @@ int dt_profile_read(int cls, const char **name, long long *launches, double *ms,
     *launches += 1; *ms += t; *flops += r.flops; *bytes += r.bytes;
   }
   return DT_OK;
-}
-
-int dt_traj_metrics(const float *X, const float *Y, int nT, int nS, int B, int E, double *out, void *stream) {
-  return launch_traj_metrics(X, Y, nT, nS, B, E, out, (hipStream_t)stream);
-}
-
-int dt_traj_wasserstein(const float *X, const float *Y, int n, int B, int E, const int32_t *index,
-                        const int32_t *index_row, int n_idx, double *out, void *stream) {
-  return launch_wasserstein(X, Y, n, B, E, index, index_row, n_idx, out, (hipStream_t)stream);
-}
-
-int dt_traj_pair_metrics(const float *X, const float *Y, int n, int B, int E, double *out_sums, double *out_w1, void *stream) {
-  return launch_pair_metrics(X, Y, n, B, E, out_sums, out_w1, (hipStream_t)stream);
-}
-
-int dt_pair_stats(const float *X, const float *Y, int n, int B, int E, double *out, void *stream) {
-  return launch_pair_stats(X, Y, n, B, E, out, (hipStream_t)stream);
-}
-
-int dt_traj_sample_mean(const float *traj, int n, int B, int E, float *out, void *stream) {
-  return launch_sample_mean(traj, n, B, E, out, (hipStream_t)stream);
-}
-
-int dt_resize_bilinear(const float *in, float *out, int planes, int h, int w, int H, int W, void *stream) {
-  return launch_resize_bilinear(in, out, planes, h, w, H, W, (hipStream_t)stream);
-}
-
-int dt_q_sample(const float *x0, const float *z, const float *coef, int n_groups, int B, int E, float *out, void *stream) {
-  return launch_q_sample(x0, z, coef, n_groups, B, E, out, (hipStream_t)stream);
-}
-
-int dt_traj_resampled_distance(const float *L, const float *S, int n_long, int n_short, int B, int E, double *out,
-                               void *stream) {
-  return launch_resampled_distance(L, S, n_long, n_short, B, E, out, (hipStream_t)stream);
 }
 
 }  // extern "C"

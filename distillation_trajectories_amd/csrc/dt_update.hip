@@ -13,6 +13,7 @@
 // reference's operation order: equal inputs give bit-identical outputs to torch CPU.
 // (HIP's __fmul_rn/__fadd_rn are header inlines compiled with contraction on, so they are not used.)
 #include "dt_update_math.h"
+#include "../../include/dt_hip_noise.h"
 
 #pragma clang fp contract(off)
 
@@ -96,13 +97,14 @@ __global__ __launch_bounds__(256) void cfg_update_kernel(const UpdateArgs a) {
   }
 }
 
-int launch_cfg_update(int rule, const float *x, const float *eu, const float *ec, const float *z,
-                      const int32_t *z_row, long long z_shift, const float coef[4], int has_noise, const float *w,
-                      float w_scalar, float *out, int B, int E, hipStream_t s) {
+extern "C" int dt_cfg_update(int rule, const float *x, const float *eu, const float *ec, const float *z, const int32_t *z_row,
+                             const float coef[4], int has_noise, const float *w, float w_scalar, float *out, int B, int E,
+                             void *stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (!x || !eu || !out || !coef) return DT_E_NULL;
   if (has_noise && !z) return DT_E_NULL;
   if (B <= 0 || E <= 0 || E % 4) return DT_E_SHAPE;
-  UpdateArgs a{x, eu, ec, z, z_row, w, out, {coef[0], coef[1], coef[2]}, w_scalar, z_shift, has_noise, B, E / 4, 0, 0, 0, 0};
+  UpdateArgs a{x, eu, ec, z, z_row, w, out, {coef[0], coef[1], coef[2]}, w_scalar, 0, has_noise, B, E / 4, 0, 0, 0, 0};
   const size_t total = (size_t)B * (E / 4);
   const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
   // algorithmic bytes: read x + read z + write x' = 3*E*4 per sample-step (+ eps reads)
@@ -162,7 +164,8 @@ __global__ __launch_bounds__(256) void q_sample_kernel(const float4 *x0, const f
   }
 }
 
-int launch_q_sample(const float *x0, const float *z, const float *coef, int n_groups, int B, int E, float *out, hipStream_t s) {
+extern "C" int dt_q_sample(const float *x0, const float *z, const float *coef, int n_groups, int B, int E, float *out, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (!x0 || !z || !coef || !out) return DT_E_NULL;
   if (n_groups <= 0 || B <= 0 || E <= 0 || E % 4) return DT_E_SHAPE;
   if (((uintptr_t)x0 | (uintptr_t)z | (uintptr_t)out) & 15 || (uintptr_t)coef & 7) return DT_E_ARG;   // float4 / float2 accesses

@@ -157,7 +157,7 @@ class UNetHandle:
         self._ws = {}
         self._consts = {}
         self._plans = {}              # (rows, H, W, images, single-pass images) -> plan id ("table:<sha1>", "tuned:<sha1>", "heuristic", "pinned")
-        self._pinned = set()          # (rows, H, W) of the shapes with launches pinned by hand (set_conv_choice)
+        self._split = {}              # (rows, H, W) -> (images, single-pass images) last named for it: see shape()
         if not _FUSED_DEFAULT:
             self.set_fused(False)
 
@@ -214,8 +214,7 @@ class UNetHandle:
         """PREC_FP32 (exact fp32 MFMA), PREC_SPLIT_BF16 (3-plane bf16 split, 6 products) or PREC_AUTO."""
         check(self.lib.dt_unet_set_precision(self.h, int(mode)), "dt_unet_set_precision")
         self._mode = {0: "fp32", 1: "split-bf16", 2: "auto"}[int(mode)]
-        self._plans.clear()               # the library drops its tuned shapes too: choices are per arithmetic mode
-        self._pinned = set()              # ... pins included: the next forward settles its plan afresh
+        self._plans.clear()               # the library drops its tuned shapes, pins included: choices are per arithmetic mode
 
     def set_fused(self, on):
         """Small models at 16x16: whole forward / whole sampler loop as one launch (dt_unet_set_fused); no-op for models
@@ -242,18 +241,34 @@ class UNetHandle:
         return (f"abi{self.PLAN_VERSION}|gfx950|prec={self._mode}|enc1={'shared' if self._shared_enc1 else 'per-pass'}|C{self.channels}"
                 f"|D{self.temb_dim}|{','.join(map(str, self.dims))}|{rows}x{H}x{W}|{imgs}/{single}")
 
-    def _read_plan(self, rows, H, W):
-        plan = []
+    def shape(self, rows, H, W, imgs=None, single=0):
+        """The full forward shape ``(rows, H, W, images, single-pass images)`` that keys a launch plan in the library and here.
+
+        A call that names the split (``forward``, ``forward_mixed``, ``sample``, ``sample_mixed``, ``ensure_plan``,
+        ``set_conv_choice(images=...)``) has it remembered for its ``(rows, H, W)``.  A call that names only the rows
+        (``conv_choices``, ``set_conv_choice`` without ``images``, ``time_conv``, ``_read_plan``) means the split remembered
+        last, else the sampler's two-pass split: ``rows // 2`` images when ``rows`` is even, ``rows`` images otherwise.
+        This is the only memory of a "last shape" anywhere; ``set_precision`` does not clear it."""
+        if imgs is None:
+            imgs, single = self._split.get((rows, H, W), (rows // 2 if rows % 2 == 0 else rows, 0))
+        else:
+            self._split[(rows, H, W)] = (imgs, single)
+        return (rows, H, W, imgs, single)
+
+    def _choices(self, key):
+        """(block, slot, bm, bn, splits, kind, skip folded, tuned) of every launch of a shape (dt_unet_conv_choice)."""
         for j in range(8):
             for slot in range(3):
-                bm, bn, sp, pr, tu = c_int(), c_int(), c_int(), c_int(), c_int()
-                check(self.lib.dt_unet_conv_choice(self.h, rows, H, W, j, slot, ctypes.byref(bm), ctypes.byref(bn),
-                                                   ctypes.byref(sp), ctypes.byref(pr), ctypes.byref(tu)), "dt_unet_conv_choice")
-                if bm.value:
-                    plan.append([j, slot, bm.value, bn.value, sp.value, pr.value & 7, 1 if pr.value & 8 else 0])
-        return plan
+                v = [c_int() for _ in range(5)]
+                check(self.lib.dt_unet_conv_choice(self.h, *key, j, slot, *map(ctypes.byref, v)), "dt_unet_conv_choice")
+                bm, bn, sp, pr, tu = (x.value for x in v)
+                if bm:
+                    yield j, slot, bm, bn, sp, pr & 7, 1 if pr & 8 else 0, bool(tu)
 
-    def _apply_plan(self, rows, H, W, plan):
+    def _read_plan(self, rows, H, W):
+        return [list(c[:7]) for c in self._choices(self.shape(rows, H, W))]
+
+    def _apply_plan(self, key, plan):
         """Pin every launch of a recorded plan; an entry this build no longer admits (or that contradicts the handle's
         arithmetic mode) is skipped, which leaves that slot on the heuristic."""
         ok = True
@@ -261,26 +276,26 @@ class UNetHandle:
             if (self._mode == "fp32") != (prec == _hip.KIND_FP32) and self._mode != "auto":
                 ok = False
                 continue
-            if self.lib.dt_unet_set_conv_choice(self.h, rows, H, W, block, slot, bm, bn, sp, prec, fuse) != 0:
+            if self.lib.dt_unet_set_conv_choice(self.h, *key, block, slot, bm, bn, sp, prec, fuse) != 0:
                 ok = False
         return ok
 
     def ensure_plan(self, rows, H, W, imgs, single, tune=None, warm=None):
-        """Settle the launch plan of a forward shape once (see ``_Plans``).  ``warm`` runs one forward of the shape
-        (real activations in the workspace) before candidates are timed.  Returns the plan id."""
-        key = (rows, H, W, imgs, single)
+        """Settle the launch plan of a forward shape once (see ``_Plans``); a shape with launches pinned by hand
+        (``set_conv_choice``) is left alone.  ``warm`` runs one forward of the shape (real activations in the workspace)
+        before candidates are timed.  Returns the plan id."""
+        key = self.shape(rows, H, W, imgs, single)
         have = self._plans.get(key)
         if have is not None and not (tune is True and not have.startswith(("tuned", "pinned"))):
             return have
-        check(self.lib.dt_unet_declare_shape(self.h, rows, H, W, imgs, single), "dt_unet_declare_shape")
         if tune is False:
             self._plans[key] = "heuristic"
             return "heuristic"
-        pkey = self.plan_key(rows, H, W, imgs, single)
+        pkey = self.plan_key(*key)
         if tune is not True:
             for source, entries in (("table", _Plans.table()), ("cache", _Plans.cache_load() or {})):
                 plan = entries.get(pkey)
-                if plan and self._apply_plan(rows, H, W, plan):
+                if plan and self._apply_plan(key, plan):
                     self._plans[key] = f"{source}:{_Plans.digest(plan)}"
                     return self._plans[key]
         measure = tune is True or (os.environ.get("DT_AUTOTUNE", "0") == "1" and rows * H * W >= AUTOTUNE_MIN_ROWS)
@@ -291,7 +306,7 @@ class UNetHandle:
             warm()
         ws = self.workspace(rows, H, W)
         with torch.cuda.device(self.device):
-            check(self.lib.dt_unet_autotune(self.h, rows, H, W, ptr(ws), c_size_t(ws.numel()), stream_ptr()), "dt_unet_autotune")
+            check(self.lib.dt_unet_autotune(self.h, *key, ptr(ws), c_size_t(ws.numel()), stream_ptr()), "dt_unet_autotune")
         plan = self._read_plan(rows, H, W)
         self._plans[key] = f"tuned:{_Plans.digest(plan)}"
         if _Plans.cache_path():
@@ -303,33 +318,32 @@ class UNetHandle:
         return {f"{k[0]}x{k[1]}x{k[2]} {k[3]}/{k[4]}": v for k, v in sorted(self._plans.items())}
 
     def set_conv_choice(self, batch_total, H, W, block, slot, bm, bn, splits=1, prec=1, fuse=0, images=None, single=0):
-        """Pin one convolution's launch choice for this forward shape (dt_unet_set_conv_choice).  A launch pinned by hand asks
-        for the layered kernels, so the handle leaves the fused small-model path (``set_fused(True)`` returns to it).
+        """Pin one convolution's launch choice for a forward shape (dt_unet_set_conv_choice); the shape's plan id becomes
+        ``"pinned"``.  A launch pinned by hand asks for the layered kernels, so the handle leaves the fused small-model path
+        (``set_fused(True)`` returns to it).
 
-        The library keys a pin by the shape's split into images, and for a row count that has not run yet it assumes the
-        two-pass split (images = batch_total / 2): ``images`` (with ``single``, the single-pass images of a mixed batch)
-        declares the split of the forward the pin is meant for, e.g. ``images=batch_total`` for a one-pass forward."""
-        if images is not None:
-            check(self.lib.dt_unet_declare_shape(self.h, batch_total, H, W, images, single), "dt_unet_declare_shape")
-        check(self.lib.dt_unet_set_conv_choice(self.h, batch_total, H, W, block, slot, bm, bn, splits, prec, fuse),
-              "dt_unet_set_conv_choice")
+        A pin belongs to the full shape: ``images`` (with ``single``, the single-pass images of a mixed batch) names the split
+        of the forward it is meant for, e.g. ``images=batch_total`` for a one-pass forward; without it, see ``shape``."""
+        key = self.shape(batch_total, H, W, images, single)
+        check(self.lib.dt_unet_set_conv_choice(self.h, *key, block, slot, bm, bn, splits, prec, fuse), "dt_unet_set_conv_choice")
         self.set_fused(False)
-        for k in [k for k in self._plans if k[:3] == (batch_total, H, W)]:
-            self._plans[k] = "pinned"
-        self._pinned.add((batch_total, H, W))
+        self._plans[key] = "pinned"
 
     def conv_choices(self, batch_total, H, W):
-        """[(block, slot, bm, bn, splits, tuned)] for reporting."""
-        out = []
-        for j in range(8):
-            for slot in range(3):
-                bm, bn, sp, pr, tu = c_int(), c_int(), c_int(), c_int(), c_int()
-                check(self.lib.dt_unet_conv_choice(self.h, batch_total, H, W, j, slot, ctypes.byref(bm), ctypes.byref(bn),
-                                                   ctypes.byref(sp), ctypes.byref(pr), ctypes.byref(tu)), "dt_unet_conv_choice")
-                if bm.value:
-                    out.append((BLOCK_NAMES[j], ("skip", "conv1", "conv2")[slot], bm.value, bn.value, sp.value,
-                                _hip.KIND_NAMES.get(pr.value & 7, "-") + ("+skip" if pr.value & 8 else ""), bool(tu.value)))
-        return out
+        """[(block, slot, bm, bn, splits, kind, tuned)] for reporting."""
+        return [(BLOCK_NAMES[j], ("skip", "conv1", "conv2")[slot], bm, bn, sp, _hip.KIND_NAMES.get(kind, "-") + ("+skip" if fold else ""), tuned)
+                for j, slot, bm, bn, sp, kind, fold, tuned in self._choices(self.shape(batch_total, H, W))]
+
+    def time_conv(self, batch_total, H, W, block, slot, bm, bn, splits=1, prec=1, fuse=0, reps=10, images=None, single=0):
+        """(milliseconds, algorithmic flops) of one convolution launch of a forward shape under an explicit choice
+        (dt_unet_time_conv: one warm launch, then the average of ``reps``), on the activations the last forward left in the
+        workspace; None where the library refuses the choice."""
+        ws = self.workspace(batch_total, H, W)
+        ms, fl = c_float(), ctypes.c_double()
+        with torch.cuda.device(self.device):
+            st = self.lib.dt_unet_time_conv(self.h, *self.shape(batch_total, H, W, images, single), block, slot, bm, bn, splits, prec,
+                                            fuse, reps, ptr(ws), c_size_t(ws.numel()), stream_ptr(), ctypes.byref(ms), ctypes.byref(fl))
+        return (ms.value, fl.value) if st == 0 else None
 
     def time_bias(self, t_values, cond_modes):
         """[rows, tb_stride] table for rows (t_values[i], cond_modes[i]); cond mode in {NONE, ZERO, ONE}.
@@ -370,15 +384,9 @@ class UNetHandle:
             with torch.cuda.device(self.device):
                 check(self.lib.dt_unet_forward(self.h, ptr(x), B, n_pass, H, W, ptr(tb), tb_div, ptr(eps), ptr(ws),
                                                c_size_t(ws.numel()), stream_ptr()), "dt_unet_forward")
-        self._settle(n_pass * B, H, W, B, 0, tune, run)
+        self.ensure_plan(n_pass * B, H, W, B, 0, tune, run)
         run()
         return eps
-
-    def _settle(self, rows, H, W, imgs, single, tune, warm):
-        if (rows, H, W) in self._pinned:      # launches pinned by hand (tests, tools): leave them alone
-            self._plans.setdefault((rows, H, W, imgs, single), "pinned")
-            return
-        self.ensure_plan(rows, H, W, imgs, single, tune, warm)
 
     def forward_mixed(self, x, tb, b_single, tb_div, tune=None):
         """eps[2B - b_single, C, H, W] of a mixed batch (dt_unet_forward_mixed): images [0, b_single) take one pass,
@@ -394,7 +402,7 @@ class UNetHandle:
             with torch.cuda.device(self.device):
                 check(self.lib.dt_unet_forward_mixed(self.h, ptr(x), B, b_single, H, W, ptr(tb), tb_div, ptr(eps), ptr(ws),
                                                      c_size_t(ws.numel()), stream_ptr()), "dt_unet_forward_mixed")
-        self._settle(rows, H, W, B, b_single, tune, run)
+        self.ensure_plan(rows, H, W, B, b_single, tune, run)
         run()
         return eps
 
@@ -409,7 +417,7 @@ class UNetHandle:
         noise_c = (c_int32 * n_steps)(*[int(bool(v)) for v in has_noise])
         shift_c = (c_int64 * n_steps)(*[int(v) for v in (z_shift if z_shift is not None else [0] * n_steps)])
         ws = self.workspace(rows, H, W)
-        if n_steps and (rows, H, W, B, b_single) not in self._plans:
+        if n_steps and self.shape(rows, H, W, B, b_single) not in self._plans:
             per_step = rows // tb_div
             self.forward_mixed(traj[0].reshape(B, self.channels, H, W), tb[:per_step].contiguous(), b_single, tb_div)
         with torch.cuda.device(self.device):
@@ -438,12 +446,12 @@ class UNetHandle:
         noise_c = (c_int32 * n_steps)(*[int(bool(v)) for v in has_noise])
         shift_c = (c_int64 * n_steps)(*[int(v) for v in (z_shift if z_shift is not None else [0] * n_steps)])
         ws = self.workspace(n_pass * B, H, W)
-        if n_steps and (n_pass * B, H, W, B, 0) not in self._plans:
+        if n_steps and self.shape(n_pass * B, H, W, B, 0) not in self._plans:
             self.forward(traj[0].reshape(B, self.channels, H, W), tb[:n_pass].contiguous(), n_pass, B)
         with torch.cuda.device(self.device):
             check(self.lib.dt_sample_trajectory(self.h, rule, B, n_pass, H, W, n_steps, ptr(tb), coef_c, noise_c,
                                                 ptr(z), ptr(z_row), shift_c, ptr(w), c_float(w_scalar), ptr(traj),
-                                                None, ptr(ws), c_size_t(ws.numel()), stream_ptr()),
+                                                ptr(ws), c_size_t(ws.numel()), stream_ptr()),
                   "dt_sample_trajectory")
         return traj
 

@@ -33,8 +33,10 @@ extern "C" {
  *    dt_sample_trajectory accepts eps_scratch_dev == NULL
  * 4: + dt_unet_set_fused / dt_unet_fused_active (small models: one launch per forward / per sampler call),
  *    dt_traj_pair_metrics (metric sums + Wasserstein term in one pass)
- * 5: + the forward-noising entry of the noise-prediction analysis, declared in include/dt_hip_noise.h */
-#define DT_ABI_VERSION 5
+ * 5: + the forward-noising entry of the noise-prediction analysis, declared in include/dt_hip_noise.h
+ * 6: dt_unet_autotune / dt_unet_conv_choice / dt_unet_set_conv_choice / dt_unet_time_conv take the forward shape in full
+ *    (images, single_pass_images after W); - dt_unet_declare_shape; dt_sample_trajectory drops eps_scratch_dev */
+#define DT_ABI_VERSION 6
 
 enum {
   DT_OK = 0,
@@ -124,12 +126,19 @@ int dt_unet_forward_mixed(const dt_unet *h, const float *x_dev, int B, int B_sin
                           const float *tb_dev, int tb_div, float *eps_dev,
                           void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* The tuning / plan hooks below name a forward shape in full: batch_total rows of H x W pictures made of `images` images, the
+ * first single_pass_images of which take one pass -- dt_unet_forward(B, n_pass) is (n_pass * B, H, W, B, 0) and
+ * dt_unet_forward_mixed(B, B_single) is (2B - B_single, H, W, B, B_single).  The split into images is part of a plan's key
+ * because enc1's launches run over the images, not the rows: two forwards with the same row count and different splits have
+ * plans of their own.  DT_E_SHAPE for rows < 1, images < 1 or pictures that are not multiples of 16 (at least 16) on a side,
+ * DT_E_ARG for rows that the images do not make up. */
+
 /* Optional: measure (HIP events, synchronises the stream) every admissible tile / tap-split of every
- * convolution launch of a forward with batch_total = n_pass*B rows and remember the fastest per layer;
- * later dt_unet_forward / dt_sample_trajectory calls with the same (batch_total, H, W) use them.
+ * convolution launch of a forward shape and remember the fastest per layer; later dt_unet_forward /
+ * dt_sample_trajectory calls of the same shape use them.
  * Results are identical up to fp32 summation order (the split changes the grouping of the tap sum). */
-int dt_unet_autotune(dt_unet *h, int batch_total, int H, int W, void *workspace_dev, size_t workspace_bytes,
-                     void *stream);
+int dt_unet_autotune(dt_unet *h, int batch_total, int H, int W, int images, int single_pass_images,
+                     void *workspace_dev, size_t workspace_bytes, void *stream);
 /* report hook: tile (bm x bn), split and launch kind in use for block (0..7), slot (0 skip, 1 conv1, 2 conv2);
  * bm = 0 means the slot has no launch of its own.  Launch kinds (the `prec` of the choice hooks):
  *   0 fp32 MFMA implicit GEMM;  1 split-bf16 implicit GEMM (operands split in the consumer);
@@ -139,26 +148,21 @@ int dt_unet_autotune(dt_unet *h, int batch_total, int H, int W, void *workspace_
  *     128 x 64 / 64 x 128 workgroup tiles, partial tiles summed in wave order;
  *   2 is retired (round 1's LDS-DMA variant) and rejected.
  * The report adds 8 when the block's 1x1 skip is folded into this conv2 launch. */
-int dt_unet_conv_choice(const dt_unet *h, int batch_total, int H, int W, int block, int slot, int *bm, int *bn,
-                        int *splits, int *prec, int *tuned);
-
-/* The tuning / plan hooks below are keyed by a forward's ROW count; how the rows split into images (images x passes, or a mixed
- * batch) decides enc1's launches, which run over the images.  The hooks use the split of the last forward with that row count;
- * this declares it beforehand (a plan applied before the first forward of a shape). */
-int dt_unet_declare_shape(dt_unet *h, int batch_total, int H, int W, int images, int single_pass_images);
+int dt_unet_conv_choice(const dt_unet *h, int batch_total, int H, int W, int images, int single_pass_images, int block,
+                        int slot, int *bm, int *bn, int *splits, int *prec, int *tuned);
 
 /* tuning / test hook: pin the launch choice of one convolution of a forward shape (the other slots keep
  * their current choice).  bm x bn in {64,128}^2, or 256 x 64 for kinds 3 / 4; not 128 x 128 for kind 5; prec: a launch
  * kind of dt_unet_conv_choice; splits in {1,3,9} taps, or 1..8 channel-chunk groups for the strip kinds 3..5 (reset to 1
  * where it does not divide); fuse only for slot 2. */
-int dt_unet_set_conv_choice(dt_unet *h, int batch_total, int H, int W, int block, int slot, int bm, int bn,
-                            int splits, int prec, int fuse);
+int dt_unet_set_conv_choice(dt_unet *h, int batch_total, int H, int W, int images, int single_pass_images, int block,
+                            int slot, int bm, int bn, int splits, int prec, int fuse);
 
 /* tuning aid: time ONE convolution launch (block, slot) of a forward shape under an explicit choice (prec: a launch
- * kind of dt_unet_conv_choice); averages `reps` launches with HIP events */
-int dt_unet_time_conv(const dt_unet *h, int batch_total, int H, int W, int block, int slot, int bm, int bn,
-                      int splits, int prec, int fuse, int reps, void *workspace_dev, size_t workspace_bytes,
-                      void *stream, float *ms, double *flops);
+ * kind of dt_unet_conv_choice); one warm launch, then the average of `reps` launches between two HIP events */
+int dt_unet_time_conv(const dt_unet *h, int batch_total, int H, int W, int images, int single_pass_images, int block,
+                      int slot, int bm, int bn, int splits, int prec, int fuse, int reps, void *workspace_dev,
+                      size_t workspace_bytes, void *stream, float *ms, double *flops);
 
 /* Convolution arithmetic.  Both variants are fp32-accurate: DT_PREC_FP32 uses the exact fp32 MFMA
  * (v_mfma_f32_32x32x2_f32); DT_PREC_SPLIT_BF16 splits every fp32 operand exactly into three bf16
@@ -210,7 +214,7 @@ int dt_cfg_update(int rule, const float *x_dev, const float *eps_u_dev, const fl
 int dt_sample_trajectory(const dt_unet *h, int rule, int B, int n_pass, int H, int W, int n_steps,
                          const float *tb_dev, const float *coef_host, const int32_t *has_noise_host,
                          const float *z_dev, const int32_t *z_row_dev, const int64_t *z_shift_host,
-                         const float *w_dev, float w_scalar, float *traj_dev, float *eps_scratch_dev,
+                         const float *w_dev, float w_scalar, float *traj_dev,
                          void *workspace_dev, size_t workspace_bytes, void *stream);
 
 /* The same loop for a mixed batch (see dt_unet_forward_mixed): images [0, B_single) are advanced with the single-pass

@@ -50,14 +50,15 @@ def handle(sf):
     return engine.UNetHandle(make_model(DiffusionUNet, cfg, sf).state_dict(), torch.device("cuda:0"))
 
 
-def report(h, rows, H, block, slot):
+def report(h, rows, H, imgs, single, block, slot):
     v = [ctypes.c_int() for _ in range(5)]
-    _hip.check(h.lib.dt_unet_conv_choice(h.h, rows, H, H, block, slot, *map(ctypes.byref, v)), "dt_unet_conv_choice")
+    _hip.check(h.lib.dt_unet_conv_choice(h.h, rows, H, H, imgs, single, block, slot, *map(ctypes.byref, v)), "dt_unet_conv_choice")
     return [x.value for x in v]
 
 
 def choice_grid(h, rows, H):
-    """status [8,3,3,2,9,6,2] and the two reports [..., 5] over GRID_AXES"""
+    """status [8,3,3,2,9,6,2] and the two reports [..., 5] over GRID_AXES, for the two-pass shape of the rows"""
+    split = (rows // 2, 0)
     axes = list(GRID_AXES.values())
     shape = tuple(len(a) for a in axes)
     status = np.zeros(shape, np.int16)
@@ -66,9 +67,9 @@ def choice_grid(h, rows, H):
     for idx in np.ndindex(shape):
         block, slot, bm, bn, sp, kind, fuse = (a[i] for a, i in zip(axes, idx))
         _hip.check(h.lib.dt_unet_set_precision(h.h, _hip.PREC_AUTO), "dt_unet_set_precision")
-        status[idx] = h.lib.dt_unet_set_conv_choice(h.h, rows, H, H, block, slot, bm, bn, sp, kind, fuse)
-        slot_rep[idx] = report(h, rows, H, block, slot)
-        skip_rep[idx] = report(h, rows, H, block, 0)
+        status[idx] = h.lib.dt_unet_set_conv_choice(h.h, rows, H, H, *split, block, slot, bm, bn, sp, kind, fuse)
+        slot_rep[idx] = report(h, rows, H, *split, block, slot)
+        skip_rep[idx] = report(h, rows, H, *split, block, 0)
     return status, slot_rep, skip_rep
 
 
@@ -94,9 +95,8 @@ def table_mismatches(h, seen):
             continue
         seen.add(key)
         h.set_precision(_hip.PREC_AUTO)
-        _hip.check(h.lib.dt_unet_declare_shape(h.h, rows, H, H, imgs, single), "dt_unet_declare_shape")
-        ok = all(h.lib.dt_unet_set_conv_choice(h.h, rows, H, H, *entry) == 0 for entry in table[key])
-        if not ok or h._read_plan(rows, H, H) != table[key]:
+        ok = all(h.lib.dt_unet_set_conv_choice(h.h, rows, H, H, imgs, single, *entry) == 0 for entry in table[key])
+        if not ok or [list(c[:7]) for c in h._choices((rows, H, H, imgs, single))] != table[key]:
             bad.append(key)
     h.set_precision(_hip.PREC_AUTO)
     return bad

@@ -1,7 +1,7 @@
 // Host-side sanitizer driver ("ASan host build"): links the library's own translation units compiled with
 // -Xarch_host -fsanitize=address,undefined (device code is NOT instrumented: GPU ASan is unavailable on this pool) and walks the
-// host code of dt_unet.hip through the C ABI -- weight packing, launch plans (heuristic, pinned, autotuned), the shape registry,
-// forward / mixed forward, the sampler loops (plain and hipGraph replay), the in-library profiler, the metric launchers and the
+// host code of dt_unet.hip through the C ABI -- weight packing, launch plans (heuristic, pinned, autotuned, keyed by the full forward
+// shape), forward / mixed forward, the sampler loops (plain and hipGraph replay), the in-library profiler, the metric launchers and the
 // argument-error paths.  Exit status 0 and "driver ok" on stdout mean no sanitizer report and no unexpected status.
 // Built by distillation_trajectories_amd/csrc/build.py (build_sanitizer_driver); run by tests/test_host_sanitize.py on the GPU box.
 #include <hip/hip_runtime.h>
@@ -112,28 +112,27 @@ int main() {
     const float fcoef[8] = {0.5f, 0.5f, 0.5f, 0.f, 0.5f, 0.5f, 0.5f, 0.f};
     const int32_t fnoise[2] = {1, 0};
     const int64_t fshift[2] = {0, B};
-    CHECK(dt_sample_trajectory(h, DT_RULE_ENGINE, B, 2, H, W, 2, tb, fcoef, fnoise, fz, nullptr, fshift, fw, 1.f, ftraj, nullptr, ws, ws_bytes, s), DT_OK);
-    CHECK(dt_sample_trajectory(h, DT_RULE_PSAMPLE, B, 1, H, W, 2, tb, fcoef, fnoise, fz, nullptr, fshift, nullptr, 1.f, ftraj, nullptr, ws, ws_bytes, s), DT_OK);
+    CHECK(dt_sample_trajectory(h, DT_RULE_ENGINE, B, 2, H, W, 2, tb, fcoef, fnoise, fz, nullptr, fshift, fw, 1.f, ftraj, ws, ws_bytes, s), DT_OK);
+    CHECK(dt_sample_trajectory(h, DT_RULE_PSAMPLE, B, 1, H, W, 2, tb, fcoef, fnoise, fz, nullptr, fshift, nullptr, 1.f, ftraj, ws, ws_bytes, s), DT_OK);
     CHECK(dt_sample_trajectory_mixed(h, DT_RULE_MANAGER, B, 2, H, W, 2, tb_mixed, 2, fcoef, fnoise, fz, nullptr, fshift, fw, ftraj, ws, ws_bytes, s), DT_OK);
     HIP(hipStreamSynchronize(s));
   }
   CHECK(dt_unet_set_fused(h, 0), DT_OK);
   if (dt_unet_fused_active(h, H, W) != 0) { fprintf(stderr, "fused path still active\n"); return 1; }
-  // ---- plans: report, pin, declare, autotune, time one launch
+  // ---- plans of the shape (2B rows, B images, no single-pass image): report, pin, autotune, time one launch
   for (int blk = 0; blk < 8; ++blk)
     for (int slot = 0; slot < 3; ++slot) {
       int bm, bn, sp, pr, tu;
-      CHECK(dt_unet_conv_choice(h, 2 * B, H, W, blk, slot, &bm, &bn, &sp, &pr, &tu), DT_OK);
+      CHECK(dt_unet_conv_choice(h, 2 * B, H, W, B, 0, blk, slot, &bm, &bn, &sp, &pr, &tu), DT_OK);
     }
-  CHECK(dt_unet_declare_shape(h, 2 * B, H, W, B, 0), DT_OK);
-  CHECK(dt_unet_declare_shape(h, 2 * B, H, W, 5, 0), DT_E_ARG);
-  CHECK(dt_unet_set_conv_choice(h, 2 * B, H, W, 1, 2, 64, 64, 1, 4, 1), DT_OK);     // K = 32 steps on a 3-chunk layer (zero-padded pack)
-  CHECK(dt_unet_set_conv_choice(h, 2 * B, H, W, 2, 1, 64, 64, 1, 5, 0), DT_OK);     // K split across waves on a 3-chunk layer
-  CHECK(dt_unet_set_conv_choice(h, 2 * B, H, W, 2, 1, 96, 64, 1, 3, 0), DT_E_ARG);
+  CHECK(dt_unet_set_conv_choice(h, 2 * B, H, W, B, 0, 1, 2, 64, 64, 1, 4, 1), DT_OK);     // K = 32 steps on a 3-chunk layer (zero-padded pack)
+  CHECK(dt_unet_set_conv_choice(h, 2 * B, H, W, 5, 0, 1, 2, 64, 64, 1, 4, 1), DT_E_ARG);  // 5 images do not make up 2B = 12 rows
+  CHECK(dt_unet_set_conv_choice(h, 2 * B, H, W, B, 0, 2, 1, 64, 64, 1, 5, 0), DT_OK);     // K split across waves on a 3-chunk layer
+  CHECK(dt_unet_set_conv_choice(h, 2 * B, H, W, B, 0, 2, 1, 96, 64, 1, 3, 0), DT_E_ARG);
   CHECK(dt_unet_forward(h, x, B, 2, H, W, tb, B, eps, ws, ws_bytes, s), DT_OK);
-  CHECK(dt_unet_autotune(h, 2 * B, H, W, ws, ws_bytes, s), DT_OK);
+  CHECK(dt_unet_autotune(h, 2 * B, H, W, B, 0, ws, ws_bytes, s), DT_OK);
   float ms = 0.f; double fl = 0.0;
-  CHECK(dt_unet_time_conv(h, 2 * B, H, W, 1, 2, 64, 64, 1, 3, 0, 2, ws, ws_bytes, s, &ms, &fl), DT_OK);
+  CHECK(dt_unet_time_conv(h, 2 * B, H, W, B, 0, 1, 2, 64, 64, 1, 3, 0, 2, ws, ws_bytes, s, &ms, &fl), DT_OK);
   CHECK(dt_unet_set_precision(h, DT_PREC_FP32), DT_OK);
   CHECK(dt_unet_forward(h, x, B, 2, H, W, tb, B, eps, ws, ws_bytes, s), DT_OK);
   CHECK(dt_unet_set_precision(h, 7), DT_E_ARG);
@@ -152,15 +151,15 @@ int main() {
   float *wv = dev_random(B, 1.f, 7.f);
 
   CHECK(dt_profile_begin(), DT_OK);
-  CHECK(dt_sample_trajectory(h, DT_RULE_PSAMPLE, B, 2, H, W, n_steps, tb, coef.data(), noise.data(), z, nullptr, shift.data(), nullptr, 3.f, traj, nullptr, ws, ws_bytes, s), DT_OK);
+  CHECK(dt_sample_trajectory(h, DT_RULE_PSAMPLE, B, 2, H, W, n_steps, tb, coef.data(), noise.data(), z, nullptr, shift.data(), nullptr, 3.f, traj, ws, ws_bytes, s), DT_OK);
   HIP(hipStreamSynchronize(s));
   CHECK(dt_profile_end(), DT_OK);
   for (int c = 0; c < dt_profile_class_count(); ++c) { const char *name; long long n; double a, b2, c2; CHECK(dt_profile_read(c, &name, &n, &a, &b2, &c2), DT_OK); }
   setenv("DT_GRAPH", "1", 1);
   for (int rep = 0; rep < 2; ++rep)
-    CHECK(dt_sample_trajectory(h, DT_RULE_ENGINE, B, 2, H, W, n_steps, tb, coef.data(), noise.data(), z, nullptr, shift.data(), wv, 1.f, traj, nullptr, ws, ws_bytes, s), DT_OK);
+    CHECK(dt_sample_trajectory(h, DT_RULE_ENGINE, B, 2, H, W, n_steps, tb, coef.data(), noise.data(), z, nullptr, shift.data(), wv, 1.f, traj, ws, ws_bytes, s), DT_OK);
   unsetenv("DT_GRAPH");
-  CHECK(dt_sample_trajectory(h, 9, B, 2, H, W, n_steps, tb, coef.data(), noise.data(), z, nullptr, shift.data(), nullptr, 3.f, traj, nullptr, ws, ws_bytes, s), DT_E_ARG);
+  CHECK(dt_sample_trajectory(h, 9, B, 2, H, W, n_steps, tb, coef.data(), noise.data(), z, nullptr, shift.data(), nullptr, 3.f, traj, ws, ws_bytes, s), DT_E_ARG);
   CHECK(dt_sample_trajectory_mixed(h, DT_RULE_ENGINE, B, 2, H, W, n_steps, tb_mixed, 2, coef.data(), noise.data(), z, nullptr, shift.data(), wv, traj, ws, ws_bytes, s), DT_OK);
   CHECK(dt_sample_trajectory_mixed(h, DT_RULE_ENGINE, B, 0, H, W, n_steps, tb_mixed, 2, coef.data(), noise.data(), z, nullptr, shift.data(), wv, traj, ws, ws_bytes, s), DT_E_ARG);
   HIP(hipStreamSynchronize(s));

@@ -200,9 +200,11 @@ class Runner:
     def act(self, j):
         return self.h.debug_activation(self.rows, self.c.H, self.c.H, j)
 
-    def report(self, j, slot):
+    def report(self, j, slot, split=None):
+        """dt_unet_conv_choice's report for the case's own shape, or for another (images, single-pass images) of its rows"""
         v = [c_int() for _ in range(5)]
-        check(self.h.lib.dt_unet_conv_choice(self.h.h, self.rows, self.c.H, self.c.H, j, slot, *map(byref, v)), "dt_unet_conv_choice")
+        imgs, single = split or (self.c.B, self.c.single)
+        check(self.h.lib.dt_unet_conv_choice(self.h.h, self.rows, self.c.H, self.c.H, imgs, single, j, slot, *map(byref, v)), "dt_unet_conv_choice")
         return tuple(x.value for x in v)
 
     def pin(self, j, slot, bm, bn, splits, kind, fuse):
@@ -278,6 +280,10 @@ def run_case(c, models, stats):
         rep = run.report(ref_j, ref_slot)
         assert rep == (64, 64, 1, _hip.KIND_FP32, 1), f"pin before the first one-pass forward was dropped: report {rep}"
         assert set(h.plan_ids().values()) == {"pinned"}, h.plan_ids()
+        # the pin belongs to that split alone: another split of the same rows (the two-pass one) settles a plan of its own
+        other = h.ensure_plan(rows, c.H, c.H, rows // 2, 0)
+        assert other != "pinned" and run.report(ref_j, ref_slot, (rows // 2, 0))[4] == 0, (other, h.plan_ids())
+        assert h.ensure_plan(rows, c.H, c.H, c.B, c.single) == "pinned" and run.report(ref_j, ref_slot) == rep, h.plan_ids()
         h.set_precision(_hip.PREC_AUTO)            # drops the pins: the next forward settles its own plan
         h.forward(run.x_dev, run.tb, c.n_pass, c.tb_div)
         assert "pinned" not in h.plan_ids().values() and run.report(ref_j, ref_slot)[4] == 0, h.plan_ids()

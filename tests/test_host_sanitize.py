@@ -1,7 +1,7 @@
 """Host-side AddressSanitizer + UndefinedBehaviorSanitizer run of the library (VERDICT r02 missing 4).
 
 csrc/_build/dt_host_sanitize (built by ``csrc/build.py::build_sanitizer_driver``, i.e. by ``__graft_entry__.build()``) links
-the library's own sources with the HOST code instrumented and walks weight packing, launch plans, the shape registry, forwards,
+the library's own sources with the HOST code instrumented and walks weight packing, launch plans, forwards,
 the sampler loops (plain, hipGraph replay, mixed batch), the profiler, the metric launchers and the argument-error paths
 through the C ABI (tests/host_sanitize/driver.cpp).  Device code is not instrumented: GPU ASan is unavailable on this pool."""
 import os

@@ -33,7 +33,7 @@ def test_header_binding_and_exports_agree():
     assert sorted(_hip.INCEPTION_SIGNATURES) == names
     assert set(names) <= exported
     lib = _hip.load(_lib_path())
-    assert lib.dt_abi_version() == _hip.ABI_VERSION == 5
+    assert lib.dt_abi_version() == _hip.ABI_VERSION == 6
     assert all(getattr(lib, n).argtypes is not None for n in names)
     assert not set(names) & (set(_hip.SIGNATURES) | set(_hip.NOISE_SIGNATURES))
 

@@ -57,7 +57,7 @@ def test_library_exports_q_sample():
     assert sorted(_hip.NOISE_SIGNATURES) == _noise_header_functions()
     assert set(_hip.NOISE_SIGNATURES) <= exported
     lib = _hip.load(path)
-    assert lib.dt_abi_version() == _hip.ABI_VERSION == 5
+    assert lib.dt_abi_version() == _hip.ABI_VERSION == 6
     assert lib.dt_q_sample.argtypes is not None
 
 

@@ -76,7 +76,7 @@ def test_header_binding_and_exports_agree():
     others = set(_hip.SIGNATURES) | set(_hip.NOISE_SIGNATURES) | set(_hip.INCEPTION_SIGNATURES)
     assert not set(names) & others
     lib = _hip.load(path)
-    assert lib.dt_abi_version() == _hip.ABI_VERSION == 5
+    assert lib.dt_abi_version() == _hip.ABI_VERSION == 6
     assert all(getattr(lib, n).argtypes is not None for n in names)
 
 

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Per-layer convolution timing table on one MI355X: every conv launch of a forward shape under chosen
 (tile, tap split, arithmetic) settings, via dt_unet_time_conv.  Usage: conv_table.py [sf] [batch_total]"""
-import ctypes
 import os
 import sys
 
@@ -22,8 +21,6 @@ h = engine.UNetHandle.for_module(m)
 x = torch.randn(Bt // 2, 3, H, H, device="cuda:0")
 tb = h.time_bias([10, 10], [_hip.COND_NONE, _hip.COND_ONE])
 h.forward(x, tb, 2, Bt // 2, tune=False)       # real activations in the workspace
-ws = h.workspace(Bt, H, H)
-lib = _hip.load()
 names = engine.BLOCK_NAMES
 print(f"sf={sf} batch_total={Bt}: us (TF/s fp32-equivalent) per launch; prec/tile/splits")
 configs = [(p, bm, bn, sp) for p in (0, 1) for (bm, bn) in ((128, 128), (128, 64), (64, 128), (64, 64)) for sp in (1, 2, 3, 4, 8, 9)]
@@ -32,12 +29,9 @@ for j in range(8):
     for slot in range(3):
         best = []
         for (prec, bm, bn, sp) in configs:
-            ms, fl = ctypes.c_float(), ctypes.c_double()
-            st = lib.dt_unet_time_conv(h.h, Bt, H, H, j, slot, bm, bn, sp, prec, 0, 10, _hip.ptr(ws), ws.numel(),
-                                       _hip.stream_ptr(), ctypes.byref(ms), ctypes.byref(fl))
-            if st != 0 or fl.value == 0:
-                continue
-            best.append((ms.value, prec, bm, bn, sp, fl.value))
+            timed = h.time_conv(Bt, H, H, j, slot, bm, bn, sp, prec)
+            if timed and timed[1]:
+                best.append((timed[0], prec, bm, bn, sp, timed[1]))
         if not best:
             continue
         best.sort()

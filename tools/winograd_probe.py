@@ -13,7 +13,6 @@ for the teacher's enc2.conv2 (256 -> 256 at 8x8) and enc1.conv2 / dec1.conv2 (12
 A 1x1 skip convolution with the wanted channel counts exists in a model whose decoder concat has Cin channels:
 dims [c, Cout, Cin / 2, Cin / 2] -> dec2's skip conv maps 2 * dims[2] = Cin -> dims[1] = Cout at 4x4.
 """
-import ctypes
 import os
 import sys
 
@@ -26,15 +25,11 @@ from distillation_trajectories_amd.models import DiffusionUNet   # noqa: E402
 from distillation_trajectories_amd.synthetic import make_model   # noqa: E402
 
 dev = torch.device("cuda:0")
-lib = _hip.load()
 
 
 def time_conv(h, Bt, block, slot, bm, bn, sp, prec, fuse=0, reps=10):
-    ws = h.workspace(Bt, 16, 16)
-    ms, fl = ctypes.c_float(), ctypes.c_double()
-    st = lib.dt_unet_time_conv(h.h, Bt, 16, 16, block, slot, bm, bn, sp, prec, fuse, reps, _hip.ptr(ws), ws.numel(), _hip.stream_ptr(),
-                               ctypes.byref(ms), ctypes.byref(fl))
-    return (ms.value * 1e3, fl.value) if st == 0 and fl.value > 0 else None
+    timed = h.time_conv(Bt, 16, 16, block, slot, bm, bn, sp, prec, fuse, reps)
+    return (timed[0] * 1e3, timed[1]) if timed and timed[1] > 0 else None
 
 
 def custom_handle(dims, D=64):
