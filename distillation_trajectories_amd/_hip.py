@@ -112,6 +112,22 @@ FID_SIGNATURES = {
                                 c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
 }
 
+# name -> (restype, argtypes) of every symbol include/dt_hip_lpips.h declares (the perceptual distance)
+LPIPS_SIGNATURES = {
+    "dt_lpips_create": (c_int, [POINTER(c_void_p), c_int, c_void_p, POINTER(c_void_p)]),
+    "dt_lpips_destroy": (None, [c_void_p]),
+    "dt_lpips_layer_shape": (c_int, [c_int, c_int, c_int, POINTER(c_int)]),
+    "dt_lpips_feature_floats": (c_size_t, [c_int, c_int]),
+    "dt_lpips_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
+    "dt_lpips_features": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p,
+                                  c_size_t, c_void_p]),
+    "dt_lpips_run_layers": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t,
+                                    c_void_p]),
+    "dt_lpips_distance": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "dt_lpips_distance_many": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                       c_void_p]),
+}
+
 
 def load(path=None):
     """Load (once) and return the library with argtypes set.  Raises HipLibraryError if absent."""
@@ -129,7 +145,7 @@ def load(path=None):
     except OSError as e:
         raise HipLibraryError(f"cannot load {path}: {e}. There is no CPU fallback.") from e
     for name, (res, args) in {**SIGNATURES, **NOISE_SIGNATURES, **INCEPTION_SIGNATURES, **PCA_SIGNATURES,
-                              **FID_SIGNATURES}.items():
+                              **FID_SIGNATURES, **LPIPS_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

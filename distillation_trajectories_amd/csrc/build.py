@@ -12,12 +12,13 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["dt_conv.hip", "dt_conv_bf16.hip", "dt_conv_strip.hip", "dt_layers.hip", "dt_update.hip", "dt_metrics.hip", "dt_fused.hip", "dt_unet.hip",
-           "dt_inception.hip", "dt_pca.hip", "dt_fid.hip"]
+           "dt_inception.hip", "dt_pca.hip", "dt_fid.hip", "dt_lpips.hip"]
 HEADERS = ["dt_internal.h", "dt_conv_forms.h", "dt_tridiag.h", "dt_conv_epilogue.h", "dt_update_math.h", "dt_fused.h", os.path.join("..", "..", "include", "dt_hip.h"),
            os.path.join("..", "..", "include", "dt_hip_noise.h"),
            os.path.join("..", "..", "include", "dt_hip_inception.h"),
            os.path.join("..", "..", "include", "dt_hip_pca.h"),
-           os.path.join("..", "..", "include", "dt_hip_fid.h")]
+           os.path.join("..", "..", "include", "dt_hip_fid.h"),
+           os.path.join("..", "..", "include", "dt_hip_lpips.h")]
 LIB = os.path.join(HERE, "libdt_hip.so")
 ARCH = "gfx950"
 
@@ -92,6 +93,7 @@ NOISE_SAN_DRIVER = os.path.join(OBJ_DIR, "dt_host_sanitize_noise")
 INCEPTION_SAN_DRIVER = os.path.join(OBJ_DIR, "dt_host_sanitize_inception")
 PCA_SAN_DRIVER = os.path.join(OBJ_DIR, "dt_host_sanitize_pca")
 FID_SAN_DRIVER = os.path.join(OBJ_DIR, "dt_host_sanitize_fid")
+LPIPS_SAN_DRIVER = os.path.join(OBJ_DIR, "dt_host_sanitize_lpips")
 
 
 def build_sanitizer_driver(verbose=False, driver="driver.cpp", out=SAN_DRIVER):
@@ -142,6 +144,12 @@ def build_fid_sanitizer_driver(verbose=False):
     return build_sanitizer_driver(verbose, driver="fid_driver.cpp", out=FID_SAN_DRIVER)
 
 
+def build_lpips_sanitizer_driver(verbose=False):
+    """The same instrumented build around tests/host_sanitize/lpips_driver.cpp, which walks every entry point of
+    include/dt_hip_lpips.h: csrc/_build/dt_host_sanitize_lpips (run by tests/test_hip_lpips.py)."""
+    return build_sanitizer_driver(verbose, driver="lpips_driver.cpp", out=LPIPS_SAN_DRIVER)
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     if "--sanitize" in sys.argv:
@@ -150,3 +158,4 @@ if __name__ == "__main__":
         print(build_inception_sanitizer_driver(verbose=True))
         print(build_pca_sanitizer_driver(verbose=True))
         print(build_fid_sanitizer_driver(verbose=True))
+        print(build_lpips_sanitizer_driver(verbose=True))

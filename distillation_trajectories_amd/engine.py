@@ -801,6 +801,25 @@ def device_fid(a, b, events=None, workspace=None):
     return out
 
 
+# ---------------------------------------------------------------------- perceptual distance (include/dt_hip_lpips.h)
+def device_lpips(handle, images0, images1, in_scale=1.0, in_shift=0.0, per_layer=False):
+    """LPIPS (v0.1, net='alex') between images0 [n0, 3, H, W] (n0 = 1: one image against all) and images1 [n1, 3, H, W]
+    on ``handle`` (lpips.LPIPSHandle): two feature passes (dt_lpips_features) and one distance launch (dt_lpips_distance).
+    ``in_scale * x + in_shift`` is applied first; (1, 0) takes images in [-1, 1] as they are.  Returns the device tensor
+    [n1], with ``per_layer`` the pair ([n1], [n1, 5])."""
+    from . import lpips
+    lpips.check_images(images0)
+    lpips.check_images(images1)
+    if tuple(images0.shape[2:]) != tuple(images1.shape[2:]):
+        raise ValueError(f"images0 {tuple(images0.shape)} and images1 {tuple(images1.shape)} differ in size")
+    if images0.shape[0] not in (1, images1.shape[0]):
+        raise ValueError(f"images0 holds {images0.shape[0]} images and images1 {images1.shape[0]}: one image, or as many")
+    H, W = images1.shape[2:]
+    p0 = handle.features(images0, in_scale, in_shift)
+    p1 = handle.features(images1, in_scale, in_shift)
+    return handle.distance(p0, p1, H, W, per_layer=per_layer)
+
+
 def resize_bilinear(images, size):
     """``torch.nn.functional.interpolate(images, size=size, mode='bilinear', align_corners=True)`` for an NCHW fp32 tensor,
     on the device (dt_resize_bilinear); a host tensor is uploaded and the result stays on the device."""

@@ -1,21 +1,76 @@
-"""Trajectory divergence (reference evaluation/metrics.py:118-183) on the HIP metric kernels, and FID (:51-116).
+"""Trajectory divergence (reference evaluation/metrics.py:118-183) on the HIP metric kernels, FID (:51-116) and LPIPS
+(:22-49).
 
 Distances, cosine similarities and path lengths come from two device reductions (dt_pair_stats, dt_traj_metrics)
 over the stacked trajectories instead of 3 x len python loops of ``torch.norm(...).item()`` / sklearn calls.
 ``compute_fid`` runs the InceptionV3 features on the device with user-supplied weights (``weights=`` or
-``DT_INCEPTION_WEIGHTS``).  LPIPS is not provided: it needs a pretrained network of its own.
+``DT_INCEPTION_WEIGHTS``).  ``compute_lpips`` runs LPIPS v0.1 (net='alex') on the device, likewise with user-supplied
+weights (``weights=`` or ``DT_LPIPS_WEIGHTS``).
 """
 import numpy as np
 import torch
 from scipy.linalg import sqrtm
 
-from .. import engine
+from .. import engine, lpips
 from ..analysis.metrics.fid_score import InceptionModel, calculate_fid_device, extract_features, stats_mode
 from ..analysis.metrics.trajectory_metrics import _metrics_device, _stack_on_device
 
 
 def _as_batch(images):
     return torch.cat(list(images)) if isinstance(images, (list, tuple)) else images
+
+
+class LPIPSModel:
+    """LPIPS v0.1 with net='alex' on ``device``: ``weights`` is a state dict of ``lpips.LPIPS(net='alex')`` or its path,
+    or the pair (torchvision AlexNet state dict, the lpips package's alex.pth) as mappings, paths or
+    ``"alexnet.pth,alex.pth"`` (default: ``$DT_LPIPS_WEIGHTS``).  ``handle`` is the device handle (lpips.LPIPSHandle)."""
+
+    def __init__(self, device, weights=None):
+        self.device = torch.device(device)
+        self.handle = lpips.LPIPSHandle(lpips.read_weights(weights), self.device)
+
+
+def lpips_distances(images1, images2, model, in_scale=2.0, in_shift=-1.0, batch_size=256, per_layer=False):
+    """LPIPS between images1[i] and images2[i] ([N, 3, H, W] each; images1 may hold ONE image, compared with every image
+    of images2), ``batch_size`` pairs per launch sequence: the device tensor [N], or [N, 5] (the five layer terms, whose
+    sum is the distance) with ``per_layer``.  ``in_scale * x + in_shift`` is applied first: the default (2, -1) maps
+    [0, 1] as compute_lpips does, (1, 0) takes [-1, 1] as it is.  A pair's value does not depend on the batching."""
+    lpips.check_images(images1)
+    lpips.check_images(images2)
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+    if tuple(images1.shape[2:]) != tuple(images2.shape[2:]) or images1.shape[0] not in (1, images2.shape[0]):
+        raise ValueError(f"images1 {tuple(images1.shape)} and images2 {tuple(images2.shape)} do not pair up: the same size, "
+                         "and one image or as many in images1")
+    h = model.handle
+    N, shared = images2.shape[0], images1.shape[0] == 1 and images2.shape[0] > 1
+    H, W = images2.shape[2:]
+    out = torch.empty(N, lpips.N_LAYERS if per_layer else 1, dtype=torch.float32, device=h.device)
+    p_shared = h.features(images1, in_scale, in_shift) if shared else None
+    for i in range(0, N, batch_size):
+        p1 = h.features(images2[i:i + batch_size], in_scale, in_shift)
+        p0 = p_shared if shared else h.features(images1[i:i + batch_size], in_scale, in_shift)
+        res = h.distance(p0, p1, H, W, per_layer=per_layer)
+        out[i:i + batch_size] = res[1] if per_layer else res[:, None]
+    return out if per_layer else out[:, 0]
+
+
+def compute_lpips(image1, image2, device, weights=None, model=None):
+    """Reference :22-49: the LPIPS distance (a Python float, lower is more similar) between two images in [0, 1],
+    [1, 3, H, W] or [3, H, W], mapped by 2x - 1 as the reference does.  ``weights`` / ``model``: an LPIPSModel to reuse,
+    else one is built on ``device`` from ``weights`` (default ``$DT_LPIPS_WEIGHTS``); without weights this raises
+    FileNotFoundError -- the reference's placeholder 0.5 is not reproduced.  More than one image per argument raises:
+    the reference's ``.item()`` only works for one; use ``lpips_distances``."""
+    a = image1[None] if isinstance(image1, torch.Tensor) and image1.dim() == 3 else image1
+    b = image2[None] if isinstance(image2, torch.Tensor) and image2.dim() == 3 else image2
+    lpips.check_images(a)
+    lpips.check_images(b)
+    if a.shape[0] != 1 or b.shape[0] != 1:
+        raise ValueError(f"compute_lpips takes one image per argument (the reference's .item()), got {a.shape[0]} and "
+                         f"{b.shape[0]}; use lpips_distances for batches")
+    if model is None:
+        model = LPIPSModel(device, weights)
+    return lpips_distances(a, b, model).item()
 
 
 def compute_fid(real_images, generated_images, device, batch_size=8, weights=None, stats=None):
