@@ -173,6 +173,41 @@ def stream_ptr():
     return c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+class DeviceHandle:
+    """A library handle on one device: the tensors moved there and given to ``<ENTRY>_create`` as a pointer array,
+    ``<ENTRY>_destroy`` when the object goes, and a workspace of ``<ENTRY>_workspace_bytes`` grown on demand."""
+    ENTRY = None            # the entry points' prefix, "dt_inception"
+    GPU_ONLY = None         # what runs on the GPU only, for the error message
+
+    def __init__(self, tensors, device):
+        import torch
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise HipLibraryError(f"{self.GPU_ONLY} on the GPU only, got device {self.device}")
+        with torch.cuda.device(self.device):
+            dev = [t.detach().to(self.device, torch.float32).contiguous() for t in tensors]
+            arr = (c_void_p * len(dev))(*[t.data_ptr() for t in dev])
+            h = c_void_p()
+            create = f"{self.ENTRY}_create"
+            check(getattr(load(), create)(arr, len(dev), stream_ptr(), ctypes.byref(h)), create)
+        self._h = h
+        self._ws = None
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            getattr(load(), f"{self.ENTRY}_destroy")(h)
+            self._h = None
+
+    def workspace(self, *shape):
+        """The workspace for a batch of ``shape`` (the arguments of ``<ENTRY>_workspace_bytes`` after the handle)."""
+        import torch
+        need = getattr(load(), f"{self.ENTRY}_workspace_bytes")(self._h, *shape)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+
 def profile_marker(marker_id):
     """Empty, recognisably named kernel on the current stream (brackets a region for external profilers)."""
     check(load().dt_profile_marker(int(marker_id), stream_ptr()), "dt_profile_marker")

@@ -2,139 +2,20 @@
 // transform_input=False, fc = Identity -- the 2048 avgpool values per image.
 //
 // Activations are NHWC fp32 between modules.  Every BasicConv2d (conv without bias + BatchNorm + ReLU) is one launch of
-// inc_conv, an implicit GEMM on exact fp32 MFMA (v_mfma_f32_32x32x2_f32): M = B*OH*OW output pixels, N = cout,
-// K = kh*kw*cin in (kh, kw, ci) order, so that with NHWC a 16-wide K chunk of an aligned layer is 16 contiguous input
-// channels of one tap.  Its epilogue applies the BatchNorm folded at create time and the ReLU and writes into a channel
-// slice of the module's concat buffer, so concatenation costs no copy.  Pools are separate small kernels.
-// There is no split-K: every output element is one k-ordered fma chain whatever the batch, so an image's features do
-// not depend on the other images in the launch.
+// featnet_conv (dt_featnet.hip), whose epilogue applies the BatchNorm folded at create time and the ReLU and writes into a
+// channel slice of the module's concat buffer, so concatenation costs no copy.  Every conv runs on a picture no smaller
+// than its kernel, so an aligned layer's tap list is the full list.  Pools are separate small kernels.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <vector>
 
 #include "../../include/dt_hip_inception.h"
+#include "dt_featnet.h"
 
 namespace {
 
-constexpr int NT = 256;             // threads of a conv block: 4 waves, 2 x 2 of 32 x 32 output tiles
-constexpr int BM = 64, BN = 64;     // block tile: output pixels x output channels
-constexpr int KC = 16;              // K chunk staged in LDS per step (8 MFMA k-steps of 2)
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-struct ConvArgs {
-  const float *x;       // [B][H][W][cin]
-  const float *w;       // [K][cout], K in (kh, kw, ci) order
-  const float *scale;   // folded BatchNorm: y = relu(scale * conv + shift)
-  const float *shift;
-  float *y;             // [M][ldy], channels [yoff, yoff + cout)
-  int M, H, W, cin, OH, OW, cout, KH, KW, stride, ph, pw, K, ldy, yoff;
-};
-
-// ALIGNED: cin % KC == 0 (every chunk lies in one tap and is 16 contiguous channels) and x is 16-byte aligned.
-template <bool ALIGNED>
-__global__ __launch_bounds__(NT) void inc_conv(ConvArgs a) {
-  __shared__ float As[KC][BM];
-  __shared__ float Bs[KC][BN];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
-
-  // A staging role: output pixel am of the tile, K elements 4 * akq .. 4 * akq + 3 of the chunk
-  const int am = t & (BM - 1), akq = t >> 6;
-  const int m = m0 + am;
-  const bool mvalid = m < a.M;
-  int b = 0, oh = 0, ow = 0;
-  if (mvalid) {
-    ow = m % a.OW;
-    const int r = m / a.OW;
-    oh = r % a.OH;
-    b = r / a.OH;
-  }
-  const int ih0 = oh * a.stride - a.ph, iw0 = ow * a.stride - a.pw;
-  const float *xb = a.x + (size_t)b * a.H * a.W * a.cin;
-  // B staging role: K row bk of the chunk, output channels 4 * (t & 15) .. + 3 (cout % 4 == 0)
-  const int bk = t >> 4, bn = (t & 15) * 4;
-  const bool nvalid = n0 + bn < a.cout;
-
-  float4 ra, rb;
-  auto load = [&](int k0) {
-    ra = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (ALIGNED) {
-      const int tap = k0 / a.cin, ci = k0 - tap * a.cin + akq * 4;
-      const int kh = tap / a.KW, kw = tap - kh * a.KW;
-      const int ih = ih0 + kh, iw = iw0 + kw;
-      if (mvalid && ih >= 0 && ih < a.H && iw >= 0 && iw < a.W)
-        ra = *reinterpret_cast<const float4 *>(xb + ((size_t)ih * a.W + iw) * a.cin + ci);
-    } else {
-      float v[4];
-      for (int j = 0; j < 4; ++j) {
-        const int k = k0 + akq * 4 + j;
-        v[j] = 0.f;
-        if (mvalid && k < a.K) {
-          const int tap = k / a.cin, ci = k - tap * a.cin;
-          const int kh = tap / a.KW, kw = tap - kh * a.KW;
-          const int ih = ih0 + kh, iw = iw0 + kw;
-          if (ih >= 0 && ih < a.H && iw >= 0 && iw < a.W) v[j] = xb[((size_t)ih * a.W + iw) * a.cin + ci];
-        }
-      }
-      ra = make_float4(v[0], v[1], v[2], v[3]);
-    }
-    const int k = k0 + bk;
-    rb = (nvalid && k < a.K) ? *reinterpret_cast<const float4 *>(a.w + (size_t)k * a.cout + n0 + bn)
-                             : make_float4(0.f, 0.f, 0.f, 0.f);
-  };
-  auto stage = [&]() {
-    As[akq * 4 + 0][am] = ra.x;
-    As[akq * 4 + 1][am] = ra.y;
-    As[akq * 4 + 2][am] = ra.z;
-    As[akq * 4 + 3][am] = ra.w;
-    *reinterpret_cast<float4 *>(&Bs[bk][bn]) = rb;
-  };
-
-  const int wm = wave & 1, wn = wave >> 1;
-  const int row = lane & 31, half = lane >> 5;
-  f32x16 acc;
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-
-  load(0);
-  for (int k0 = 0; k0 < a.K; k0 += KC) {
-    stage();
-    __syncthreads();
-    if (k0 + KC < a.K) load(k0 + KC);      // next chunk's global loads overlap this chunk's MFMAs
-#pragma unroll
-    for (int s = 0; s < KC / 2; ++s) {
-      const float av = As[2 * s + half][wm * 32 + row];
-      const float bv = Bs[2 * s + half][wn * 32 + row];
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
-    }
-    __syncthreads();
-  }
-
-  // D map of the 32x32 MFMA: column (output channel) = lane & 31, row (pixel) = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
-  const int n = n0 + wn * 32 + row;
-  if (n >= a.cout) return;
-  const float sc = a.scale[n], sh = a.shift[n];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int mm = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-    if (mm < a.M) a.y[(size_t)mm * a.ldy + a.yoff + n] = fmaxf(fmaf(acc[r], sc, sh), 0.f);
-  }
-}
-
-// max pool 3x3 stride 2, no padding: x [B][H][W][C] -> y [B][OH][OW][ldy], channels [yoff, yoff + C)
-__global__ void inc_maxpool(const float *x, int B, int H, int W, int C, int OH, int OW, float *y, int ldy, int yoff) {
-  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= (size_t)B * OH * OW * C) return;
-  const int c = (int)(e % C);
-  const size_t pix = e / C;
-  const int ow = (int)(pix % OW), oh = (int)(pix / OW % OH), b = (int)(pix / OW / OH);
-  const float *xb = x + ((size_t)b * H * W) * C + c;
-  float v = xb[((size_t)(2 * oh) * W + 2 * ow) * C];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) v = fmaxf(v, xb[((size_t)(2 * oh + i) * W + 2 * ow + j) * C]);
-  y[pix * ldy + yoff + c] = v;
-}
+using namespace featnet;
 
 // avg pool 3x3 stride 1 padding 1, count_include_pad: every window divides by 9.  x, y [B][H][W][C]
 __global__ void inc_avgpool(const float *x, int B, int H, int W, int C, float *y) {
@@ -186,14 +67,6 @@ __global__ void inc_preprocess(const float *x, int B, int H, int W, float in_sca
   }
 }
 
-// torchvision [cout][cin][kh][kw] -> [(kh, kw, ci)][cout]
-__global__ void inc_relayout(const float *src, int cout, int cin, int KH, int KW, float *dst) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= cout * cin * KH * KW) return;
-  const int kw = e % KW, kh = e / KW % KH, ci = e / (KW * KH) % cin, co = e / (KW * KH * cin);
-  dst[((size_t)(kh * KW + kw) * cin + ci) * cout + co] = src[e];
-}
-
 // BatchNorm (eps 1e-3, running statistics) as a per-channel scale and shift, in float64
 __global__ void inc_fold_bn(const float *g, const float *bta, const float *mean, const float *var, int n, float *scale,
                             float *shift) {
@@ -224,7 +97,6 @@ struct Net {
     convs.push_back({cin, cout, kh, kw, stride, ph, pw});
     return (int)convs.size() - 1;
   }
-  static int out_size(int n, int k, int s, int p) { return (n + 2 * p - k) / s + 1; }
   void need(int buf, size_t floats) { scratch[buf] = floats > scratch[buf] ? floats : scratch[buf]; }
   // one BasicConv2d from buffer src (H x W x cin) to dst, channel offset yoff; returns the output size
   void op_conv(int ci, int src, int dst, int H, int W, int yoff = 0) {
@@ -338,7 +210,7 @@ struct Net {
     begin(8, 8, 2048);                  // avgpool
     ops.push_back({OP_MEAN, -1, BUF_IN, BUF_OUT, 8, 8, 2048, 0});
     end(1, 1, 2048);
-    for (int b = 0; b < N_BUF; ++b) scratch[b] = (scratch[b] + 63) / 64 * 64;     // 256-byte aligned slices
+    for (int b = 0; b < N_BUF; ++b) scratch[b] = round64(scratch[b]);
     scratch[BUF_IN] = scratch[BUF_OUT] = scratch[BUF_IN] > scratch[BUF_OUT] ? scratch[BUF_IN] : scratch[BUF_OUT];
   }
 };
@@ -348,16 +220,12 @@ const Net &net() {
   return n;
 }
 
-int hip_status(hipError_t e) { return e == hipSuccess ? DT_OK : (int)e; }
-
 size_t ws_floats(int B) {
   const Net &n = net();
   size_t f = 0;
   for (int b = 0; b < N_BUF; ++b) f += n.scratch[b] * (size_t)B;
   return f;
 }
-
-bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
@@ -373,18 +241,11 @@ int launch_conv(const dt_inception *h, int ci, const float *x, int B, int H, int
   const ConvDesc &d = net().convs[ci];
   ConvArgs a;
   a.x = x, a.w = h->slab + h->w_off[ci], a.scale = h->slab + h->s_off[ci], a.shift = h->slab + h->t_off[ci], a.y = y;
-  a.H = H, a.W = W, a.cin = d.cin, a.cout = d.cout, a.KH = d.kh, a.KW = d.kw, a.stride = d.stride, a.ph = d.ph, a.pw = d.pw;
-  a.OH = Net::out_size(H, d.kh, d.stride, d.ph), a.OW = Net::out_size(W, d.kw, d.stride, d.pw);
-  a.M = B * a.OH * a.OW, a.K = d.kh * d.kw * d.cin, a.ldy = ldy, a.yoff = yoff;
-  const dim3 grid((a.M + BM - 1) / BM, (d.cout + BN - 1) / BN);
-  if (d.cin % KC == 0 && aligned16(x))
-    hipLaunchKernelGGL(inc_conv<true>, grid, dim3(NT), 0, s, a);
-  else
-    hipLaunchKernelGGL(inc_conv<false>, grid, dim3(NT), 0, s, a);
-  return hip_status(hipGetLastError());
+  a.B = B, a.H = H, a.W = W, a.cin = d.cin, a.cout = d.cout, a.KH = d.kh, a.KW = d.kw, a.stride = d.stride, a.ph = d.ph, a.pw = d.pw;
+  a.ldy = ldy, a.yoff = yoff, a.xs = (long long)H * W * d.cin;
+  a.ys = (long long)out_size(H, d.kh, d.stride, d.ph) * out_size(W, d.kw, d.stride, d.pw) * ldy;
+  return featnet_launch_conv(a, s);
 }
-
-unsigned blocks(size_t n, int t) { return (unsigned)((n + t - 1) / t); }
 
 int run(const dt_inception *h, int first, int last, const float *in, int B, float *out, float *ws, hipStream_t s) {
   const Net &n = net();
@@ -406,10 +267,7 @@ int run(const dt_inception *h, int first, int last, const float *in, int B, floa
         const int ldy = o.dst == BUF_OUT ? m.OC : n.convs[o.conv].cout;
         st = launch_conv(h, o.conv, src, B, o.H, o.W, y, ldy, o.yoff, s);
       } else if (o.kind == OP_MAXPOOL) {
-        const int OH = Net::out_size(o.H, 3, 2, 0), OW = Net::out_size(o.W, 3, 2, 0);
-        hipLaunchKernelGGL(inc_maxpool, dim3(blocks((size_t)B * OH * OW * o.C, 256)), dim3(256), 0, s, src, B, o.H, o.W,
-                           o.C, OH, OW, y, m.OC, o.yoff);
-        st = hip_status(hipGetLastError());
+        st = featnet_launch_maxpool(src, (size_t)o.H * o.W * o.C, B, o.H, o.W, o.C, y, m.OC, o.yoff, s);
       } else if (o.kind == OP_AVGPOOL) {
         hipLaunchKernelGGL(inc_avgpool, dim3(blocks((size_t)B * o.H * o.W * o.C, 256)), dim3(256), 0, s, src, B, o.H,
                            o.W, o.C, y);
@@ -461,23 +319,20 @@ int dt_inception_create(const float *const *params, int n_params, void *stream, 
   const Net &n = net();
   if ((int)n.convs.size() != DT_INCEPTION_N_CONVS || (int)n.mods.size() != DT_INCEPTION_N_MODULES) return DT_E_ARG;
   dt_inception *h = new dt_inception;
-  size_t off = 0;
-  auto take = [&](size_t floats) { const size_t o = off; off += (floats + 63) / 64 * 64; return o; };
+  Slab slab;
   for (int i = 0; i < DT_INCEPTION_N_CONVS; ++i) {
     const ConvDesc &d = n.convs[i];
-    h->w_off[i] = take((size_t)d.cout * d.cin * d.kh * d.kw);
-    h->s_off[i] = take(d.cout);
-    h->t_off[i] = take(d.cout);
+    h->w_off[i] = slab.take((size_t)d.cout * d.cin * d.kh * d.kw);
+    h->s_off[i] = slab.take(d.cout);
+    h->t_off[i] = slab.take(d.cout);
   }
-  hipError_t e = hipMalloc((void **)&h->slab, off * sizeof(float));
+  hipError_t e = hipMalloc((void **)&h->slab, slab.floats * sizeof(float));
   if (e != hipSuccess) { delete h; return (int)e; }
   hipStream_t s = (hipStream_t)stream;
   for (int i = 0; i < DT_INCEPTION_N_CONVS && e == hipSuccess; ++i) {
     const ConvDesc &d = n.convs[i];
     const float *const *p = params + 5 * i;
-    const int nw = d.cout * d.cin * d.kh * d.kw;
-    hipLaunchKernelGGL(inc_relayout, dim3(blocks(nw, 256)), dim3(256), 0, s, p[0], d.cout, d.cin, d.kh, d.kw,
-                       h->slab + h->w_off[i]);
+    featnet_launch_relayout(p[0], d.cout, d.cin, d.kh, d.kw, h->slab + h->w_off[i], s);
     hipLaunchKernelGGL(inc_fold_bn, dim3(blocks(d.cout, 256)), dim3(256), 0, s, p[1], p[2], p[3], p[4], d.cout,
                        h->slab + h->s_off[i], h->slab + h->t_off[i]);
     e = hipGetLastError();

@@ -1,14 +1,9 @@
 // LPIPS v0.1, net='alex' (include/dt_hip_lpips.h): AlexNet features up to the fifth ReLU and the perceptual distance.
 //
-// Activations are NHWC fp32.  Every conv is one launch of lp_conv, an implicit GEMM on exact fp32 MFMA
-// (v_mfma_f32_32x32x2_f32): M = N*OH*OW output pixels, cout columns, K in (kh, kw, ci) order; the epilogue is
-// bias + ReLU and writes straight into the image's feature pack.  There is no split-K: every output element is one
-// k-ordered fma chain, so an image's pack does not depend on the batch.
-// What differs from the Inception convs: images are addressed through a per-image stride (the taps live inside the
-// packs), conv1 has cin 3 and K = 363 (the unaligned gather), and on small pictures most taps of conv2..5 lie in the
-// padding for EVERY pixel of the launch (at 31..34-pixel inputs conv3..5 see a 1 x 1 picture: 8 of 9 taps).  The host
-// lists the taps that touch the picture for at least one output pixel and the kernel walks only those; a skipped tap
-// would have added fma(0, w, acc) to every chain.
+// Activations are NHWC fp32.  Every conv is one launch of featnet_conv (dt_featnet.hip) with the bias as its shift and no
+// scale; it reads its images through a per-image stride (the taps live inside the packs) and writes straight into the
+// image's feature pack.  conv1 has cin 3 and K = 363 (the unaligned gather); conv2..5 walk the host's tap list, which on
+// small pictures leaves out the taps that lie in the padding for every pixel of the launch.
 // The distance (lp_distance) is one pass over both packs, one workgroup per pair, in the difference form, in fp64.
 #include <hip/hip_runtime.h>
 
@@ -16,145 +11,18 @@
 #include <cstdint>
 
 #include "../../include/dt_hip_lpips.h"
+#include "dt_featnet.h"
 
 namespace {
 
-constexpr int NT = 256;             // threads of a conv block: 4 waves, 2 x 2 of 32 x 32 output tiles
-constexpr int BM = 64, BN = 64;     // block tile: output pixels x output channels
-constexpr int KC = 16;              // K chunk staged in LDS per step (8 MFMA k-steps of 2)
-constexpr int MAX_TAPS = 25;        // tap lists are kept for conv2..5 (5 x 5 at most)
-constexpr int NL = DT_LPIPS_N_LAYERS;
+using namespace featnet;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+constexpr int NT = 256;             // threads of a distance block: 4 waves
+constexpr int NL = DT_LPIPS_N_LAYERS;
 
 struct LayerDesc { int cin, cout, k, stride, pad, pool; };     // pool: a 3x3 s2 max pool in front of the conv
 constexpr LayerDesc kLayers[NL] = {{3, 64, 11, 4, 2, 0}, {64, 192, 5, 1, 2, 1}, {192, 384, 3, 1, 1, 1},
                                    {384, 256, 3, 1, 1, 0}, {256, 256, 3, 1, 1, 0}};
-
-struct ConvArgs {
-  const float *x;       // image b at x + b * xs: [H][W][cin]
-  const float *w;       // [(kh, kw, ci)][cout]
-  const float *bias;
-  float *y;             // image b at y + b * ys: [OH][OW][cout]
-  long long xs, ys;
-  int M, P, H, W, cin, OW, cout, KW, stride, pad;
-  int K;                // walked K: ntaps * cin with a tap list (ALIGNED), KH * KW * cin without
-  int tap[MAX_TAPS];    // kh * KW + kw of the walked taps, ascending
-};
-
-// ALIGNED: cin % KC == 0 (every chunk lies in one tap and is 16 contiguous channels), x and xs 16-byte aligned; walks a.tap.
-template <bool ALIGNED>
-__global__ __launch_bounds__(NT) void lp_conv(ConvArgs a) {
-  __shared__ float As[KC][BM];
-  __shared__ float Bs[KC][BN];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
-
-  // A staging role: output pixel am of the tile, K elements 4 * akq .. 4 * akq + 3 of the chunk
-  const int am = t & (BM - 1), akq = t >> 6;
-  const int m = m0 + am;
-  const bool mvalid = m < a.M;
-  int b = 0, oh = 0, ow = 0;
-  if (mvalid) {
-    b = m / a.P;
-    const int pix = m - b * a.P;
-    oh = pix / a.OW;
-    ow = pix - oh * a.OW;
-  }
-  const int ih0 = oh * a.stride - a.pad, iw0 = ow * a.stride - a.pad;
-  const float *xb = a.x + (size_t)b * a.xs;
-  // B staging role: K row bk of the chunk, output channels 4 * (t & 15) .. + 3 (cout % 4 == 0)
-  const int bk = t >> 4, bn = (t & 15) * 4;
-  const bool nvalid = n0 + bn < a.cout;
-
-  float4 ra, rb;
-  auto load = [&](int k0) {
-    ra = make_float4(0.f, 0.f, 0.f, 0.f);
-    int wrow;                                 // row of a.w that K element k0 + bk is
-    if (ALIGNED) {
-      const int ti = k0 / a.cin, c0 = k0 - ti * a.cin;
-      const int tap = a.tap[ti];
-      const int kh = tap / a.KW, kw = tap - kh * a.KW;
-      const int ih = ih0 + kh, iw = iw0 + kw;
-      if (mvalid && ih >= 0 && ih < a.H && iw >= 0 && iw < a.W)
-        ra = *reinterpret_cast<const float4 *>(xb + ((size_t)ih * a.W + iw) * a.cin + c0 + akq * 4);
-      wrow = tap * a.cin + c0 + bk;
-    } else {
-      float v[4];
-      for (int j = 0; j < 4; ++j) {
-        const int k = k0 + akq * 4 + j;
-        v[j] = 0.f;
-        if (mvalid && k < a.K) {
-          const int tap = k / a.cin, ci = k - tap * a.cin;
-          const int kh = tap / a.KW, kw = tap - kh * a.KW;
-          const int ih = ih0 + kh, iw = iw0 + kw;
-          if (ih >= 0 && ih < a.H && iw >= 0 && iw < a.W) v[j] = xb[((size_t)ih * a.W + iw) * a.cin + ci];
-        }
-      }
-      ra = make_float4(v[0], v[1], v[2], v[3]);
-      wrow = k0 + bk;
-    }
-    rb = (nvalid && k0 + bk < a.K) ? *reinterpret_cast<const float4 *>(a.w + (size_t)wrow * a.cout + n0 + bn)
-                                  : make_float4(0.f, 0.f, 0.f, 0.f);
-  };
-  auto stage = [&]() {
-    As[akq * 4 + 0][am] = ra.x;
-    As[akq * 4 + 1][am] = ra.y;
-    As[akq * 4 + 2][am] = ra.z;
-    As[akq * 4 + 3][am] = ra.w;
-    *reinterpret_cast<float4 *>(&Bs[bk][bn]) = rb;
-  };
-
-  const int wm = wave & 1, wn = wave >> 1;
-  const int row = lane & 31, half = lane >> 5;
-  f32x16 acc;
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-
-  load(0);
-  for (int k0 = 0; k0 < a.K; k0 += KC) {
-    stage();
-    __syncthreads();
-    if (k0 + KC < a.K) load(k0 + KC);      // next chunk's global loads overlap this chunk's MFMAs
-#pragma unroll
-    for (int s = 0; s < KC / 2; ++s) {
-      const float av = As[2 * s + half][wm * 32 + row];
-      const float bv = Bs[2 * s + half][wn * 32 + row];
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
-    }
-    __syncthreads();
-  }
-
-  // D map of the 32x32 MFMA: column (output channel) = lane & 31, row (pixel) = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
-  const int n = n0 + wn * 32 + row;
-  if (n >= a.cout) return;
-  const float bias = a.bias[n];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int mm = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-    if (mm < a.M) {
-      const int bb = mm / a.P, pix = mm - bb * a.P;
-      a.y[(size_t)bb * a.ys + (size_t)pix * a.cout + n] = fmaxf(acc[r] + bias, 0.f);
-    }
-  }
-}
-
-// max pool 3x3 stride 2, no padding, four channels per thread: image b at x + b * xs [H][W][C] -> y [N][OH][OW][C]
-__global__ void lp_maxpool(const float *x, long long xs, int N, int H, int W, int C, int OH, int OW, float *y) {
-  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int C4 = C / 4;
-  if (e >= (size_t)N * OH * OW * C4) return;
-  const int c = (int)(e % C4) * 4;
-  const size_t pix = e / C4;
-  const int ow = (int)(pix % OW), oh = (int)(pix / OW % OH), b = (int)(pix / OW / OH);
-  const float *xb = x + (size_t)b * xs + c;
-  float4 v = *reinterpret_cast<const float4 *>(xb + ((size_t)(2 * oh) * W + 2 * ow) * C);
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) {
-      const float4 u = *reinterpret_cast<const float4 *>(xb + ((size_t)(2 * oh + i) * W + 2 * ow + j) * C);
-      v.x = fmaxf(v.x, u.x), v.y = fmaxf(v.y, u.y), v.z = fmaxf(v.z, u.z), v.w = fmaxf(v.w, u.w);
-    }
-  *reinterpret_cast<float4 *>(y + pix * C + c) = v;
-}
 
 __constant__ float kShift[3] = {-.030f, -.088f, -.188f};
 __constant__ float kScale[3] = {.458f, .448f, .450f};
@@ -168,14 +36,6 @@ __global__ void lp_scale(const float *x, int N, int HW, float in_scale, float in
     const float v = fmaf(in_scale, x[(b * 3 + c) * HW + p], in_shift);
     y[e * 3 + c] = (v - kShift[c]) / kScale[c];
   }
-}
-
-// [cout][cin][kh][kw] -> [(kh, kw, ci)][cout]
-__global__ void lp_relayout(const float *src, int cout, int cin, int KH, int KW, float *dst) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= cout * cin * KH * KW) return;
-  const int kw = e % KW, kh = e / KW % KH, ci = e / (KW * KH) % cin, co = e / (KW * KH * cin);
-  dst[((size_t)(kh * KW + kw) * cin + ci) * cout + co] = src[e];
 }
 
 // ------------------------------------------------------------------------------------------------------ the distance
@@ -252,17 +112,8 @@ __global__ __launch_bounds__(NT) void lp_distance(DistArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------------- host side
-int hip_status(hipError_t e) { return e == hipSuccess ? DT_OK : (int)e; }
-bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-unsigned blocks(size_t n, int t) { return (unsigned)((n + t - 1) / t); }
-size_t round64(size_t f) { return (f + 63) / 64 * 64; }
-int out_size(int n, int k, int s, int p) { return (n + 2 * p - k) / s + 1; }
 bool size_ok(int H, int W) {
   return H >= DT_LPIPS_MIN_SIZE && H <= DT_LPIPS_MAX_SIZE && W >= DT_LPIPS_MIN_SIZE && W <= DT_LPIPS_MAX_SIZE;
-}
-bool overlap(const void *p, size_t pb, const void *q, size_t qb) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return a < b + qb && b < a + pb;
 }
 
 // every size of the network for an H x W image
@@ -313,41 +164,15 @@ struct dt_lpips {
 
 namespace {
 
-// the taps (kh * k + kw, ascending) of which at least one output pixel's input lies inside the picture
-int tap_list(const LayerDesc &d, int H, int W, int OH, int OW, int *tap) {
-  int n = 0;
-  for (int kh = 0; kh < d.k; ++kh) {
-    bool vh = false;
-    for (int o = 0; o < OH && !vh; ++o) vh = o * d.stride - d.pad + kh >= 0 && o * d.stride - d.pad + kh < H;
-    if (!vh) continue;
-    for (int kw = 0; kw < d.k; ++kw) {
-      bool vw = false;
-      for (int o = 0; o < OW && !vw; ++o) vw = o * d.stride - d.pad + kw >= 0 && o * d.stride - d.pad + kw < W;
-      if (vw) tap[n++] = kh * d.k + kw;
-    }
-  }
-  return n;
-}
-
 int launch_conv(const dt_lpips *h, int l, const float *x, size_t xs, int N, int H, int W, float *y, size_t ys,
                 hipStream_t s) {
   const LayerDesc &d = kLayers[l];
   ConvArgs a;
-  a.x = x, a.w = h->slab + h->w_off[l], a.bias = h->slab + h->b_off[l], a.y = y;
+  a.x = x, a.w = h->slab + h->w_off[l], a.scale = nullptr, a.shift = h->slab + h->b_off[l], a.y = y;
   a.xs = (long long)xs, a.ys = (long long)ys;
-  a.H = H, a.W = W, a.cin = d.cin, a.cout = d.cout, a.KW = d.k, a.stride = d.stride, a.pad = d.pad;
-  const int OH = out_size(H, d.k, d.stride, d.pad);
-  a.OW = out_size(W, d.k, d.stride, d.pad);
-  a.P = OH * a.OW, a.M = N * a.P;
-  for (int i = 0; i < MAX_TAPS; ++i) a.tap[i] = 0;
-  const bool aligned = d.cin % KC == 0 && d.k * d.k <= MAX_TAPS && aligned16(x) && xs % 4 == 0;
-  a.K = aligned ? tap_list(d, H, W, OH, a.OW, a.tap) * d.cin : d.k * d.k * d.cin;
-  const dim3 grid((a.M + BM - 1) / BM, (d.cout + BN - 1) / BN);
-  if (aligned)
-    hipLaunchKernelGGL(lp_conv<true>, grid, dim3(NT), 0, s, a);
-  else
-    hipLaunchKernelGGL(lp_conv<false>, grid, dim3(NT), 0, s, a);
-  return hip_status(hipGetLastError());
+  a.B = N, a.H = H, a.W = W, a.cin = d.cin, a.cout = d.cout, a.KH = a.KW = d.k, a.stride = d.stride, a.ph = a.pw = d.pad;
+  a.ldy = d.cout, a.yoff = 0;
+  return featnet_launch_conv(a, s);
 }
 
 // layers [first, last): layer l reads `in` (stride in_stride) when l == first, else tap l - 1, and writes tap[l] (stride ts[l])
@@ -361,10 +186,7 @@ int run(const dt_lpips *h, int first, int last, const float *in, size_t in_strid
     const float *x = l == first ? in : tap[l - 1];
     size_t xs = l == first ? in_stride : ts[l - 1];
     if (d.pool) {
-      const size_t n4 = (size_t)N * sh.ih[l] * sh.iw[l] * (d.cin / 4);
-      hipLaunchKernelGGL(lp_maxpool, dim3(blocks(n4, 256)), dim3(256), 0, s, x, (long long)xs, N, sh.ph[l], sh.pw[l], d.cin,
-                         sh.ih[l], sh.iw[l], pool[l]);
-      const int st = hip_status(hipGetLastError());
+      const int st = featnet_launch_maxpool(x, xs, N, sh.ph[l], sh.pw[l], d.cin, pool[l], d.cin, 0, s);
       if (st != DT_OK) return st;
       x = pool[l], xs = sh.pool_floats(l);
     }
@@ -421,22 +243,19 @@ int dt_lpips_create(const float *const *params, int n_params, void *stream, dt_l
   for (int i = 0; i < n_params; ++i)
     if (!params[i]) return DT_E_NULL;
   dt_lpips *h = new dt_lpips;
-  size_t off = 0;
-  auto take = [&](size_t floats) { const size_t o = off; off += round64(floats); return o; };
+  Slab slab;
   for (int l = 0; l < NL; ++l) {
     const LayerDesc &d = kLayers[l];
-    h->w_off[l] = take((size_t)d.cout * d.cin * d.k * d.k);
-    h->b_off[l] = take(d.cout);
+    h->w_off[l] = slab.take((size_t)d.cout * d.cin * d.k * d.k);
+    h->b_off[l] = slab.take(d.cout);
   }
-  for (int l = 0; l < NL; ++l) h->lin_off[l] = take(kLayers[l].cout);
-  hipError_t e = hipMalloc((void **)&h->slab, off * sizeof(float));
+  for (int l = 0; l < NL; ++l) h->lin_off[l] = slab.take(kLayers[l].cout);
+  hipError_t e = hipMalloc((void **)&h->slab, slab.floats * sizeof(float));
   if (e != hipSuccess) { delete h; return (int)e; }
   hipStream_t s = (hipStream_t)stream;
   for (int l = 0; l < NL && e == hipSuccess; ++l) {
     const LayerDesc &d = kLayers[l];
-    const int nw = d.cout * d.cin * d.k * d.k;
-    hipLaunchKernelGGL(lp_relayout, dim3(blocks(nw, 256)), dim3(256), 0, s, params[2 * l], d.cout, d.cin, d.k, d.k,
-                       h->slab + h->w_off[l]);
+    featnet_launch_relayout(params[2 * l], d.cout, d.cin, d.k, d.k, h->slab + h->w_off[l], s);
     e = hipGetLastError();
     if (e == hipSuccess)
       e = hipMemcpyAsync(h->slab + h->b_off[l], params[2 * l + 1], d.cout * sizeof(float), hipMemcpyDeviceToDevice, s);

@@ -8,14 +8,13 @@ state dict, or named by ``DT_INCEPTION_WEIGHTS``; nothing is ever downloaded.
 This module holds the torchvision key table, the state-dict loader that checks a state dict against it, and
 ``InceptionHandle``, the device handle (BatchNorm is folded on the device at create time).
 """
-import ctypes
 import os
-from ctypes import c_int, c_void_p
+from ctypes import c_int
 
 import torch
 
 from . import _hip
-from ._hip import HipLibraryError, check, ptr, stream_ptr
+from ._hip import check, ptr, stream_ptr
 
 WEIGHTS_ENV = "DT_INCEPTION_WEIGHTS"
 WEIGHTS_FILE = "inception_v3_google-0cc3c7bd.pth"
@@ -191,34 +190,12 @@ def module_shape(m):
     return tuple(a), tuple(b)
 
 
-class InceptionHandle:
-    """The network's weights on one device (dt_inception_create) and a workspace grown on demand."""
+class InceptionHandle(_hip.DeviceHandle):
+    """The network's weights on one device (dt_inception_create) and a workspace grown on demand: ``workspace(B)``."""
+    ENTRY, GPU_ONLY = "dt_inception", "InceptionV3 features run"
 
     def __init__(self, state_dict, device):
-        tensors = check_state_dict(state_dict)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise HipLibraryError(f"InceptionV3 features run on the GPU only, got device {self.device}")
-        lib = _hip.load()
-        with torch.cuda.device(self.device):
-            dev = [t.detach().to(self.device, torch.float32).contiguous() for t in tensors]
-            arr = (c_void_p * len(dev))(*[t.data_ptr() for t in dev])
-            h = c_void_p()
-            check(lib.dt_inception_create(arr, len(dev), stream_ptr(), ctypes.byref(h)), "dt_inception_create")
-        self._h = h
-        self._ws = None
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            _hip.load().dt_inception_destroy(h)
-            self._h = None
-
-    def workspace(self, B):
-        need = _hip.load().dt_inception_workspace_bytes(self._h, B)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._ws
+        super().__init__(check_state_dict(state_dict), device)
 
     def _images(self, images):
         check_images(images)

@@ -16,15 +16,14 @@ checked against the packages themselves.  If a release names a tensor differentl
   (b) a pair: torchvision's AlexNet state dict (``features.{0,3,6,8,10}.*``; ``classifier.*`` ignored) and the ``lpips``
       package's ``alex.pth`` (``lin{k}.model.1.weight``).
 """
-import ctypes
 import os
 from collections.abc import Mapping
-from ctypes import c_int, c_void_p
+from ctypes import c_int
 
 import torch
 
 from . import _hip
-from ._hip import HipLibraryError, check, ptr, stream_ptr
+from ._hip import check, ptr, stream_ptr
 
 WEIGHTS_ENV = "DT_LPIPS_WEIGHTS"
 N_LAYERS = 5
@@ -186,34 +185,12 @@ def split_pack(pack, H, W):
     return out
 
 
-class LPIPSHandle:
-    """The network's weights on one device (dt_lpips_create) and a workspace grown on demand."""
+class LPIPSHandle(_hip.DeviceHandle):
+    """The network's weights on one device (dt_lpips_create) and a workspace grown on demand: ``workspace(N, H, W)``."""
+    ENTRY, GPU_ONLY = "dt_lpips", "LPIPS runs"
 
     def __init__(self, weights, device):
-        tensors = check_state_dict(weights)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise HipLibraryError(f"LPIPS runs on the GPU only, got device {self.device}")
-        lib = _hip.load()
-        with torch.cuda.device(self.device):
-            dev = [t.detach().to(self.device, torch.float32).contiguous() for t in tensors]
-            arr = (c_void_p * len(dev))(*[t.data_ptr() for t in dev])
-            h = c_void_p()
-            check(lib.dt_lpips_create(arr, len(dev), stream_ptr(), ctypes.byref(h)), "dt_lpips_create")
-        self._h = h
-        self._ws = None
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            _hip.load().dt_lpips_destroy(h)
-            self._h = None
-
-    def workspace(self, N, H, W):
-        need = _hip.load().dt_lpips_workspace_bytes(self._h, N, H, W)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._ws
+        super().__init__(check_state_dict(weights), device)
 
     def features(self, images, in_scale=1.0, in_shift=0.0, out=None):
         """[N, feature_floats(H, W)] fp32 on the device for images [N, 3, H, W]: ``in_scale * x + in_shift``, the

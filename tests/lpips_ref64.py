@@ -50,7 +50,8 @@ def scale_input(sd, x, in_scale=1.0, in_shift=0.0):
     """[N, 3, H, W] -> the scaling layer's output, in the state dict's dtype."""
     dt = _dtype(sd)
     v = in_scale * x.to(dt) + in_shift
-    return (v - torch.tensor(SHIFT, dtype=dt).view(1, 3, 1, 1)) / torch.tensor(SCALE, dtype=dt).view(1, 3, 1, 1)
+    shift, scale = (torch.tensor(c, dtype=dt, device=v.device).view(1, 3, 1, 1) for c in (SHIFT, SCALE))
+    return (v - shift) / scale
 
 
 def run_layer(sd, l, x):
