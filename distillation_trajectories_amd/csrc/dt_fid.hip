@@ -9,7 +9,7 @@
 //      sit on a large common offset that must not reach the product (fid_cross_kernel);
 //   3. S = M M^T (n_a <= n_b) or M^T M, side m = min(n_a, n_b), upper-triangle tiles mirrored into full symmetric
 //      storage (fid_square_kernel);
-//   4. Householder tridiagonalisation of S (dt_tridiag.h, shared with dt_pca.hip), Gershgorin bounds (fid_bounds_kernel)
+//   4. Householder tridiagonalisation of S (dt_dense64.h, shared with dt_pca.hip), Gershgorin bounds (fid_bounds_kernel)
 //      and all m eigenvalues by Sturm-count bisection, one thread per eigenvalue, one wave per workgroup so that the m
 //      latency-bound chains spread over m / 64 compute units (fid_bisect_kernel);
 //   5. cross = sum sqrt(max(lambda, 0)) / sqrt((n_a - 1)(n_b - 1)) in index order, fid and the outputs (fid_finish_kernel).
@@ -18,22 +18,12 @@
 
 #include "../../include/dt_hip_fid.h"
 #include "dt_internal.h"
-#include "dt_tridiag.h"
+#include "dt_dense64.h"
 
 namespace {
 
 constexpr int kWave = 64;
 enum { MISC_DMU2 = 0, MISC_TRA, MISC_TRB, MISC_GL, MISC_GU, MISC_PIVMIN, MISC_TNORM, MISC_COUNT = 16 };
-
-struct Sets {
-  const float *a, *b;
-  long long a_ps, a_rs, b_ps, b_rs;
-  int n_a, n_b;
-};
-
-__device__ inline const float *set_row(const Sets &R, int set, int p, int i) {
-  return set == 0 ? R.a + p * R.a_ps + i * R.a_rs : R.b + p * R.b_ps + i * R.b_rs;
-}
 
 // per-problem workspace (doubles), after a head of P ints (the non-finite flag) rounded to 256 bytes
 struct Layout {
@@ -41,7 +31,7 @@ struct Layout {
   size_t mean, csq, misc, M, S, v, pv, e, tau, d, lam;
   int m;
   __host__ __device__ Layout(int P, int n_a, int n_b, int D) {
-    head = ((size_t)P * sizeof(int) + 255) / 256 * 256;
+    head = flag_head_bytes(P);
     m = n_a < n_b ? n_a : n_b;
     const size_t N = (size_t)m;
     mean = 0;                                   // [2][D]
@@ -62,30 +52,23 @@ struct Layout {
 
 // ---------------------------------------------------------------------------------------------- 1. means and traces
 // one thread per quad of columns, rows in order; blockIdx.z is the set
-__global__ __launch_bounds__(kWave) void fid_mean_kernel(Sets R, int D, double *ws, size_t per, int *flag) {
+__global__ __launch_bounds__(kWave) void fid_mean_kernel(Rows R, int D, double *ws, size_t per, int *flag) {
   const int p = blockIdx.y, set = blockIdx.z;
   const int q = blockIdx.x * kWave + threadIdx.x;
   if (4 * q >= D) return;
-  const int n = set == 0 ? R.n_a : R.n_b;
-  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-  bool bad = false;
-  for (int i = 0; i < n; ++i) {
-    const float4 x = reinterpret_cast<const float4 *>(set_row(R, set, p, i))[q];
-    bad |= !(isfinite(x.x) && isfinite(x.y) && isfinite(x.z) && isfinite(x.w));
-    s0 += x.x; s1 += x.y; s2 += x.z; s3 += x.w;
-  }
-  const double nr = (double)n;
-  const double m0 = s0 / nr, m1 = s1 / nr, m2 = s2 / nr, m3 = s3 / nr;
+  double m[4];
+  const bool bad = quad_mean(R, p, set, set, q, m);
+  const RowSet S = row_set(R, set, p);
   double c0 = 0.0, c1 = 0.0, c2 = 0.0, c3 = 0.0;
-  for (int i = 0; i < n; ++i) {
-    const float4 x = reinterpret_cast<const float4 *>(set_row(R, set, p, i))[q];
-    const double d0 = (double)x.x - m0, d1 = (double)x.y - m1, d2 = (double)x.z - m2, d3 = (double)x.w - m3;
+  for (int i = 0; i < S.n; ++i) {
+    const float4 x = reinterpret_cast<const float4 *>(S.row0 + i * S.rs)[q];
+    const double d0 = (double)x.x - m[0], d1 = (double)x.y - m[1], d2 = (double)x.z - m[2], d3 = (double)x.w - m[3];
     c0 = fma(d0, d0, c0); c1 = fma(d1, d1, c1); c2 = fma(d2, d2, c2); c3 = fma(d3, d3, c3);
   }
   double *base = ws + (size_t)p * per;
-  double *m = base + (size_t)set * D + 4 * (size_t)q;
+  double *mo = base + (size_t)set * D + 4 * (size_t)q;
   double *c = base + (size_t)(2 + set) * D + 4 * (size_t)q;
-  m[0] = m0; m[1] = m1; m[2] = m2; m[3] = m3;
+  mo[0] = m[0]; mo[1] = m[1]; mo[2] = m[2]; mo[3] = m[3];
   c[0] = c0; c[1] = c1; c[2] = c2; c[3] = c3;
   if (bad) atomicOr(flag + p, 1);
 }
@@ -114,122 +97,54 @@ __global__ __launch_bounds__(kThreads) void fid_stats_kernel(int n_a, int n_b, i
 }
 
 // ---------------------------------------------------------------------------------------------- 2. M = A_c B_c^T
-// 64 x 64 output tile per workgroup, 4 x 4 outputs per thread (rows ty + 16a, columns tx + 16b), 16 columns of D per
-// LDS stage.  Each output is one fp64 FMA chain over e = 0 .. D-1 in order.
-__global__ __launch_bounds__(kThreads) void fid_cross_kernel(Sets R, int D, double *ws, size_t per, const int *flag,
+// 64 x 64 tiles (tile_product, dt_dense64.h) over the D columns, rows centred as they are loaded
+__global__ __launch_bounds__(kThreads) void fid_cross_kernel(Rows R, int D, double *ws, size_t per, const int *flag,
                                                              int ntb) {
   const int p = blockIdx.y;
   if (flag[p]) return;
   const int bi = blockIdx.x / ntb, bj = blockIdx.x % ntb;
-  __shared__ double As[16][64], Bs[16][64];
-  const int t = threadIdx.x, tx = t % 16, ty = t / 16;
-  const int lr = t / 4, lq = t % 4;
+  const int lr = threadIdx.x / 4, lq = threadIdx.x % 4;
   const int ra = bi * 64 + lr, rb = bj * 64 + lr;
-  const float *pa = ra < R.n_a ? set_row(R, 0, p, ra) : nullptr;
-  const float *pb = rb < R.n_b ? set_row(R, 1, p, rb) : nullptr;
   double *base = ws + (size_t)p * per;
-  const double *ma = base, *mb = base + D;
   double acc[4][4] = {};
-  for (int e0 = 0; e0 < D; e0 += 16) {
-    const int e = e0 + 4 * lq;
-    double va[4] = {0.0, 0.0, 0.0, 0.0}, vb[4] = {0.0, 0.0, 0.0, 0.0};
-    if (e < D) {
-      if (pa) {
-        const float4 x = *reinterpret_cast<const float4 *>(pa + e);
-        va[0] = (double)x.x - ma[e]; va[1] = (double)x.y - ma[e + 1];
-        va[2] = (double)x.z - ma[e + 2]; va[3] = (double)x.w - ma[e + 3];
-      }
-      if (pb) {
-        const float4 x = *reinterpret_cast<const float4 *>(pb + e);
-        vb[0] = (double)x.x - mb[e]; vb[1] = (double)x.y - mb[e + 1];
-        vb[2] = (double)x.z - mb[e + 2]; vb[3] = (double)x.w - mb[e + 3];
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      As[4 * lq + c][lr] = va[c];
-      Bs[4 * lq + c][lr] = vb[c];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int kk = 0; kk < 16; ++kk) {
-      double a[4], b[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) { a[u] = As[kk][ty + 16 * u]; b[u] = Bs[kk][tx + 16 * u]; }
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int w = 0; w < 4; ++w) acc[u][w] = fma(a[u], b[w], acc[u][w]);
-    }
-    __syncthreads();
-  }
-  double *M = base + Layout(0, R.n_a, R.n_b, D).M;
-#pragma unroll
-  for (int u = 0; u < 4; ++u)
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const int r = bi * 64 + ty + 16 * u, c = bj * 64 + tx + 16 * w;
-      if (r < R.n_a && c < R.n_b) M[(size_t)r * R.n_b + c] = acc[u][w];
-    }
+  tile_product(D, lr, lq, CentredRow{ra < R.n_a ? row_ptr(R, p, ra) : nullptr, base, D},
+               CentredRow{rb < R.n_b ? row_ptr(R, p, R.n_a + rb) : nullptr, base + D, D}, acc);
+  store_tile<false>(base + Layout(0, R.n_a, R.n_b, D).M, R.n_a, R.n_b, bi, bj, acc);
 }
 
 // ---------------------------------------------------------------------------------------------- 3. S = M M^T | M^T M
 // The same tile, over the upper triangle of S.  Row i of the factor is row i of M (TRANS = false: k runs along the row,
 // kdim = n_b) or column i of M (TRANS = true: kdim = n_a); the loads are coalesced along whichever index is contiguous.
 // S[i][j] and S[j][i] of a diagonal tile are the same chain of the same products, so S is exactly symmetric.
+// Loader for tile_product: entry k of row r of the factor (live: r < m), one per call
+template <bool TRANS>
+struct FactorRow {
+  const double *M;
+  int n_b, kdim, r;
+  bool live;
+  static constexpr int W = 1;
+  __device__ void operator()(int k, double (&v)[1]) const {
+    v[0] = live && k < kdim ? (TRANS ? M[(size_t)k * n_b + r] : M[(size_t)r * n_b + k]) : 0.0;
+  }
+};
+
 template <bool TRANS>
 __global__ __launch_bounds__(kThreads) void fid_square_kernel(int n_a, int n_b, int D, double *ws, size_t per,
                                                               const int *flag, int nt) {
   const int p = blockIdx.y;
   if (flag[p]) return;
-  int tile = blockIdx.x, bi = 0;
-  while (tile >= nt - bi) { tile -= nt - bi; ++bi; }
-  const int bj = bi + tile;
-  __shared__ double As[16][64], Bs[16][64];
+  int bi, bj;
+  upper_tile(blockIdx.x, nt, bi, bj);
   const Layout L(0, n_a, n_b, D);
   const int m = L.m, kdim = TRANS ? n_a : n_b;
   double *base = ws + (size_t)p * per;
-  const double *M = base + L.M;
-  const int t = threadIdx.x, tx = t % 16, ty = t / 16;
+  const int t = threadIdx.x;
   const int lr = TRANS ? t % 64 : t / 4, lq = TRANS ? t / 64 : t % 4;
   const int ra = bi * 64 + lr, rb = bj * 64 + lr;
   double acc[4][4] = {};
-  for (int k0 = 0; k0 < kdim; k0 += 16) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const int k = k0 + 4 * lq + c;
-      double va = 0.0, vb = 0.0;
-      if (k < kdim) {
-        if (ra < m) va = TRANS ? M[(size_t)k * n_b + ra] : M[(size_t)ra * n_b + k];
-        if (rb < m) vb = TRANS ? M[(size_t)k * n_b + rb] : M[(size_t)rb * n_b + k];
-      }
-      As[4 * lq + c][lr] = va;
-      Bs[4 * lq + c][lr] = vb;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int kk = 0; kk < 16; ++kk) {
-      double a[4], b[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) { a[u] = As[kk][ty + 16 * u]; b[u] = Bs[kk][tx + 16 * u]; }
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int w = 0; w < 4; ++w) acc[u][w] = fma(a[u], b[w], acc[u][w]);
-    }
-    __syncthreads();
-  }
-  double *S = base + L.S;
-#pragma unroll
-  for (int u = 0; u < 4; ++u)
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const int r = bi * 64 + ty + 16 * u, c = bj * 64 + tx + 16 * w;
-      if (r < m && c < m) {
-        S[(size_t)r * m + c] = acc[u][w];
-        if (bi != bj) S[(size_t)c * m + r] = acc[u][w];
-      }
-    }
+  tile_product(kdim, lr, lq, FactorRow<TRANS>{base + L.M, n_b, kdim, ra, ra < m},
+               FactorRow<TRANS>{base + L.M, n_b, kdim, rb, rb < m}, acc);
+  store_tile<true>(base + L.S, m, m, bi, bj, acc);
 }
 
 // ---------------------------------------------------------------------------------------------- 4. eigenvalues
@@ -240,31 +155,14 @@ __global__ __launch_bounds__(kThreads) void fid_bounds_kernel(int n_a, int n_b, 
   const int p = blockIdx.x;
   if (flag[p]) return;
   const Layout L(0, n_a, n_b, D);
-  const int n = L.m, t = threadIdx.x;
   double *base = ws + (size_t)p * per;
-  const double *A = base + L.S;
-  double *d = base + L.d, *e = base + L.e;
-  for (int i = t; i < n; i += kThreads) d[i] = A[(size_t)i * n + i];
-  if (t == 0) e[n - 2] = A[(size_t)(n - 1) * n + n - 2];
-  __syncthreads();
-  double lo = INFINITY, hi = -INFINITY, e2max = 0.0;
-  for (int i = t; i < n; i += kThreads) {
-    const double off = (i > 0 ? fabs(e[i - 1]) : 0.0) + (i < n - 1 ? fabs(e[i]) : 0.0);
-    lo = fmin(lo, d[i] - off);
-    hi = fmax(hi, d[i] + off);
-    if (i < n - 1) e2max = fmax(e2max, e[i] * e[i]);
-  }
-  double gl = block_min(lo, red), gu = block_max(hi, red);
-  const double pivmin = DBL_MIN * fmax(1.0, block_max(e2max, red));
-  const double tnorm = fmax(fabs(gl), fabs(gu));
-  gl -= 2.0 * DBL_EPSILON * tnorm * n + 2.0 * pivmin;
-  gu += 2.0 * DBL_EPSILON * tnorm * n + 2.0 * pivmin;
-  if (t == 0) {
+  const Spectrum sp = tridiagonal_spectrum(base + L.S, L.m, base + L.d, base + L.e, red);
+  if (threadIdx.x == 0) {
     double *misc = base + L.misc;
-    misc[MISC_GL] = gl;
-    misc[MISC_GU] = gu;
-    misc[MISC_PIVMIN] = pivmin;
-    misc[MISC_TNORM] = tnorm;
+    misc[MISC_GL] = sp.gl;
+    misc[MISC_GU] = sp.gu;
+    misc[MISC_PIVMIN] = sp.pivmin;
+    misc[MISC_TNORM] = sp.tnorm;
   }
 }
 
@@ -285,19 +183,9 @@ __global__ __launch_bounds__(kWave) void fid_bisect_kernel(int n_a, int n_b, int
   const int j = blockIdx.x * kWave + threadIdx.x;
   if (j >= n) return;
   const double *misc = base + L.misc;
-  const double pivmin = misc[MISC_PIVMIN], tnorm = misc[MISC_TNORM];
-  double a = misc[MISC_GL], b = misc[MISC_GU];
-  if (tnorm == 0.0) {                            // the zero matrix (a set without variance): every eigenvalue is 0
-    base[L.lam + j] = 0.0;
-    return;
-  }
-  for (int it = 0; it < 256; ++it) {
-    const double tol = 2.0 * DBL_EPSILON * fmax(fabs(a), fabs(b)) + DBL_EPSILON * tnorm;
-    if (b - a <= tol) break;
-    const double mid = 0.5 * (a + b);
-    if (sturm_below(ds, es, n, mid, pivmin) > j) b = mid; else a = mid;
-  }
-  base[L.lam + j] = 0.5 * (a + b);
+  const Spectrum sp{misc[MISC_GL], misc[MISC_GU], misc[MISC_PIVMIN], misc[MISC_TNORM]};
+  // the zero matrix (a set without variance): every eigenvalue is 0
+  base[L.lam + j] = sp.tnorm == 0.0 ? 0.0 : bisect_eigenvalue(ds, es, n, j, sp);
 }
 
 // ---------------------------------------------------------------------------------------------- 5. the distance
@@ -333,10 +221,6 @@ __global__ __launch_bounds__(kThreads) void fid_finish_kernel(int n_a, int n_b, 
   }
 }
 
-bool aligned16(const void *ptr, long long s1, long long s2) {
-  return ((uintptr_t)ptr & 15) == 0 && s1 % 4 == 0 && s2 % 4 == 0;
-}
-
 bool shape_ok(int P, int n_a, int n_b, int D) {
   return P >= 1 && P <= 65535 && n_a >= 2 && n_b >= 2 && n_a <= 32768 && n_b <= 32768 &&
          (n_a < n_b ? n_a : n_b) <= DT_FID_MAX_SIDE && D >= 4 && D % 4 == 0 && D <= (1 << 20);
@@ -361,7 +245,7 @@ extern "C" int dt_fid_distance(const float *a_dev, int n_a, long long a_pstride,
   if (ws_bytes < L.bytes(P)) return DT_E_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
   if (events) DT_HIP_TRY(hipEventRecord((hipEvent_t)events[0], s));
-  const Sets R{a_dev, b_dev, a_pstride, a_rstride, b_pstride, b_rstride, n_a, n_b};
+  const Rows R{a_dev, b_dev, a_pstride, a_rstride, b_pstride, b_rstride, n_a, n_b};
   int *flag = (int *)ws;
   double *wd = (double *)((char *)ws + L.head);
   const int m = L.m;

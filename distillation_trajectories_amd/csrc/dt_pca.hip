@@ -19,26 +19,16 @@
 
 #include "../../include/dt_hip_pca.h"
 #include "dt_internal.h"
-#include "dt_tridiag.h"
+#include "dt_dense64.h"
 
 namespace {
-
-struct Rows {
-  const float *a, *b;
-  long long a_ps, a_rs, b_ps, b_rs;
-  int n_a, n;
-};
-
-__device__ inline const float *row_ptr(const Rows &R, int p, int i) {
-  return i < R.n_a ? R.a + p * R.a_ps + i * R.a_rs : R.b + p * R.b_ps + (long long)(i - R.n_a) * R.b_rs;
-}
 
 // per-problem workspace (doubles), after a head of 2 * P ints (non-finite flag, status) rounded to 256 bytes
 struct Layout {
   size_t head, per;
   size_t mean, G, v, pv, d, e, tau, lam, misc, Z, lu, V;
   __host__ __device__ Layout(int P, int n, int E, int k) {
-    head = ((size_t)2 * P * sizeof(int) + 255) / 256 * 256;
+    head = flag_head_bytes(2 * P);
     const size_t N = (size_t)n;
     mean = 0;
     G = mean + (size_t)E;
@@ -63,84 +53,30 @@ __global__ __launch_bounds__(kThreads) void pca_mean_kernel(Rows R, int E, doubl
   const int p = blockIdx.y;
   const int q = blockIdx.x * kThreads + threadIdx.x;
   if (4 * q >= E) return;
-  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-  bool bad = false;
-  for (int i = 0; i < R.n; ++i) {
-    const float4 x = reinterpret_cast<const float4 *>(row_ptr(R, p, i))[q];
-    bad |= !(isfinite(x.x) && isfinite(x.y) && isfinite(x.z) && isfinite(x.w));
-    s0 += x.x; s1 += x.y; s2 += x.z; s3 += x.w;
-  }
-  const double nr = (double)R.n;
-  double *m = ws + (size_t)p * per + 4 * (size_t)q;
-  m[0] = s0 / nr; m[1] = s1 / nr; m[2] = s2 / nr; m[3] = s3 / nr;
-  float4 o = make_float4((float)m[0], (float)m[1], (float)m[2], (float)m[3]);
-  reinterpret_cast<float4 *>(mean_out + (size_t)p * E)[q] = o;
+  double m[4];
+  const bool bad = quad_mean(R, p, 0, 1, q, m);
+  double *out = ws + (size_t)p * per + 4 * (size_t)q;
+  out[0] = m[0]; out[1] = m[1]; out[2] = m[2]; out[3] = m[3];
+  reinterpret_cast<float4 *>(mean_out + (size_t)p * E)[q] = make_float4((float)m[0], (float)m[1], (float)m[2], (float)m[3]);
   if (bad) atomicOr(flag + p, 1);
 }
 
 // ---------------------------------------------------------------------------------------------- 2. centred Gram
-// 64 x 64 output tile per workgroup, 4 x 4 outputs per thread (rows ty + 16a, columns tx + 16b), 16 columns of E per
-// LDS stage.  Each output is one fp64 FMA chain over e = 0 .. E-1 in order.
+// G = Xc Xc^T over the upper triangle of 64 x 64 tiles (tile_product, dt_dense64.h), rows centred as they are loaded
 __global__ __launch_bounds__(kThreads) void pca_gram_kernel(Rows R, int E, double *ws, size_t per, const int *flag,
                                                             int nt) {
   const int p = blockIdx.y;
   if (flag[p]) return;
-  int tile = blockIdx.x, bi = 0;
-  while (tile >= nt - bi) { tile -= nt - bi; ++bi; }
-  const int bj = bi + tile;
-  __shared__ double As[16][64], Bs[16][64];
-  const int t = threadIdx.x, tx = t % 16, ty = t / 16;
-  const int lr = t / 4, lq = t % 4;
-  const int n = R.n;
+  int bi, bj;
+  upper_tile(blockIdx.x, nt, bi, bj);
+  const int lr = threadIdx.x / 4, lq = threadIdx.x % 4;
+  const int n = R.n_a + R.n_b;
   const int ra = bi * 64 + lr, rb = bj * 64 + lr;
-  const float *pa = ra < n ? row_ptr(R, p, ra) : nullptr;
-  const float *pb = rb < n ? row_ptr(R, p, rb) : nullptr;
   const double *mean = ws + (size_t)p * per;
   double acc[4][4] = {};
-  for (int e0 = 0; e0 < E; e0 += 16) {
-    const int e = e0 + 4 * lq;
-    double va[4] = {0.0, 0.0, 0.0, 0.0}, vb[4] = {0.0, 0.0, 0.0, 0.0};
-    if (e < E) {
-      if (pa) {
-        const float4 x = *reinterpret_cast<const float4 *>(pa + e);
-        va[0] = (double)x.x - mean[e]; va[1] = (double)x.y - mean[e + 1];
-        va[2] = (double)x.z - mean[e + 2]; va[3] = (double)x.w - mean[e + 3];
-      }
-      if (pb) {
-        const float4 x = *reinterpret_cast<const float4 *>(pb + e);
-        vb[0] = (double)x.x - mean[e]; vb[1] = (double)x.y - mean[e + 1];
-        vb[2] = (double)x.z - mean[e + 2]; vb[3] = (double)x.w - mean[e + 3];
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      As[4 * lq + c][lr] = va[c];
-      Bs[4 * lq + c][lr] = vb[c];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int kk = 0; kk < 16; ++kk) {
-      double a[4], b[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) { a[u] = As[kk][ty + 16 * u]; b[u] = Bs[kk][tx + 16 * u]; }
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int w = 0; w < 4; ++w) acc[u][w] = fma(a[u], b[w], acc[u][w]);
-    }
-    __syncthreads();
-  }
-  double *G = ws + (size_t)p * per + E;
-#pragma unroll
-  for (int u = 0; u < 4; ++u)
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const int r = bi * 64 + ty + 16 * u, c = bj * 64 + tx + 16 * w;
-      if (r < n && c < n) {
-        G[(size_t)r * n + c] = acc[u][w];
-        if (bi != bj) G[(size_t)c * n + r] = acc[u][w];
-      }
-    }
+  tile_product(E, lr, lq, CentredRow{ra < n ? row_ptr(R, p, ra) : nullptr, mean, E},
+               CentredRow{rb < n ? row_ptr(R, p, rb) : nullptr, mean, E}, acc);
+  store_tile<true>(ws + (size_t)p * per + E, n, n, bi, bj, acc);
 }
 
 // trace(G) and the status word: non-finite input, then zero total variance
@@ -161,7 +97,7 @@ __global__ __launch_bounds__(kThreads) void pca_status_kernel(int n, int E, int 
 }
 
 // ---------------------------------------------------------------------------------------------- 3. eigen stage
-// The tridiagonalisation kernels and sturm_below are in dt_tridiag.h (shared with dt_fid.hip).
+// The tridiagonalisation kernels, the spectrum bounds and the bisection are in dt_dense64.h (shared with dt_fid.hip).
 
 __device__ inline double start_entry(int i, int j) {
   unsigned h = (unsigned)i * 2654435761u ^ ((unsigned)j + 1u) * 40503u;
@@ -181,37 +117,10 @@ __global__ __launch_bounds__(kThreads) void pca_eigen_kernel(int n, int E, int k
   const double *A = base + L.G;
   double *d = base + L.d, *e = base + L.e, *lam = base + L.lam, *Z = base + L.Z;
   const int t = threadIdx.x;
-  for (int i = t; i < n; i += kThreads) d[i] = A[(size_t)i * n + i];
-  if (t == 0) e[n - 2] = A[(size_t)(n - 1) * n + n - 2];
-  __syncthreads();
-
-  double lo = INFINITY, hi = -INFINITY, nrm = 0.0, e2max = 0.0;
-  for (int i = t; i < n; i += kThreads) {
-    const double off = (i > 0 ? fabs(e[i - 1]) : 0.0) + (i < n - 1 ? fabs(e[i]) : 0.0);
-    lo = fmin(lo, d[i] - off);
-    hi = fmax(hi, d[i] + off);
-    nrm = fmax(nrm, fabs(d[i]) + off);
-    if (i < n - 1) e2max = fmax(e2max, e[i] * e[i]);
-  }
-  double gl = block_min(lo, red), gu = block_max(hi, red);
-  const double onenrm = block_max(nrm, red);
-  const double pivmin = DBL_MIN * fmax(1.0, block_max(e2max, red));
-  const double tnorm = fmax(fabs(gl), fabs(gu));
-  gl -= 2.0 * DBL_EPSILON * tnorm * n + 2.0 * pivmin;
-  gu += 2.0 * DBL_EPSILON * tnorm * n + 2.0 * pivmin;
-
-  // bisection: lambda_j is eigenvalue n-1-j in ascending order
-  if (t < k) {
-    const int m = n - 1 - t;
-    double a = gl, b = gu;
-    for (int it = 0; it < 256; ++it) {
-      const double tol = 2.0 * DBL_EPSILON * fmax(fabs(a), fabs(b)) + DBL_EPSILON * tnorm;
-      if (b - a <= tol) break;
-      const double mid = 0.5 * (a + b);
-      if (sturm_below(d, e, n, mid, pivmin) > m) b = mid; else a = mid;
-    }
-    lam[t] = 0.5 * (a + b);
-  }
+  double onenrm;
+  const Spectrum sp = tridiagonal_spectrum(A, n, d, e, red, &onenrm);
+  const double tnorm = sp.tnorm;
+  if (t < k) lam[t] = bisect_eigenvalue(d, e, n, n - 1 - t, sp);      // lambda_j is eigenvalue n-1-j in ascending order
   __syncthreads();
 
   // inverse iteration (dstein-like), one thread: LU with partial pivoting of T - x I, five solves per vector, each
@@ -316,7 +225,7 @@ __global__ __launch_bounds__(kThreads) void pca_components_kernel(Rows R, int E,
   __shared__ double Us[DT_PCA_MAX_K][64];
   const int p = blockIdx.y;
   if (st[p]) return;
-  const int n = R.n;
+  const int n = R.n_a + R.n_b;
   const Layout L(0, n, E, k);
   double *base = ws + (size_t)p * per;
   const int e = blockIdx.x * kThreads + threadIdx.x;
@@ -415,7 +324,7 @@ __global__ __launch_bounds__(kThreads) void pca_project_kernel(Rows R, int E, in
                                                                float *scores) {
   const int p = blockIdx.y, w = threadIdx.x / 64, lane = threadIdx.x % 64;
   const int r = blockIdx.x * (kThreads / 64) + w;
-  if (r >= R.n) return;
+  if (r >= R.n_a + R.n_b) return;
   const float4 *x = reinterpret_cast<const float4 *>(row_ptr(R, p, r));
   const float4 *m = reinterpret_cast<const float4 *>(mean + p * mean_ps);
   const float *cb = comp + p * comp_ps;
@@ -437,12 +346,8 @@ __global__ __launch_bounds__(kThreads) void pca_project_kernel(Rows R, int E, in
   for (int j = 0; j < DT_PCA_MAX_K; ++j)
     if (j < k) {
       const double s = wave_sum(acc[j]);
-      if (lane == 0) scores[((size_t)p * R.n + r) * k + j] = (float)s;
+      if (lane == 0) scores[((size_t)p * (R.n_a + R.n_b) + r) * k + j] = (float)s;
     }
-}
-
-bool aligned16(const void *ptr, long long s1, long long s2) {
-  return ((uintptr_t)ptr & 15) == 0 && s1 % 4 == 0 && s2 % 4 == 0;
 }
 
 bool fit_shape_ok(int P, int n, int E, int k) {
@@ -474,7 +379,7 @@ extern "C" int dt_pca_fit(const float *a_dev, int n_a, long long a_pstride, long
   if (ws_bytes < L.bytes(P)) return DT_E_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
   if (events) DT_HIP_TRY(hipEventRecord((hipEvent_t)events[0], s));
-  const Rows R{a_dev, n_b > 0 ? b_dev : a_dev, a_pstride, a_rstride, b_pstride, b_rstride, n_a, n};
+  const Rows R{a_dev, n_b > 0 ? b_dev : a_dev, a_pstride, a_rstride, b_pstride, b_rstride, n_a, n_b};
   int *flag = (int *)ws, *st = flag + P;
   double *wd = (double *)((char *)ws + L.head);
   DT_HIP_TRY(hipMemsetAsync(ws, 0, L.head, s));
@@ -512,7 +417,7 @@ extern "C" int dt_pca_project(const float *a_dev, int n_a, long long a_pstride, 
       !aligned16(mean_dev, mean_pstride, 0) || !aligned16(components_dev, comp_pstride, 0))
     return DT_E_ARG;
   const int n = n_a + n_b;
-  const Rows R{n_a > 0 ? a_dev : b_dev, n_b > 0 ? b_dev : a_dev, a_pstride, a_rstride, b_pstride, b_rstride, n_a, n};
+  const Rows R{n_a > 0 ? a_dev : b_dev, n_b > 0 ? b_dev : a_dev, a_pstride, a_rstride, b_pstride, b_rstride, n_a, n_b};
   const int per_block = kThreads / 64;
   pca_project_kernel<<<dim3((n + per_block - 1) / per_block, P), kThreads, 0, (hipStream_t)stream>>>(
       R, E, k, mean_dev, mean_pstride, components_dev, comp_pstride, scores_dev);

@@ -580,31 +580,50 @@ def device_sample_mean(traj):
     return out
 
 
-# ---------------------------------------------------------------------- PCA (include/dt_hip_pca.h)
-PCA_MAX_K = 16
-
-
-def _pca_rows(t, name):
-    """[n, P, E] view of a step-major tensor (a 2-D [n, E] tensor is one problem); shape errors are ValueErrors."""
+# ---------------------------------------------------------------------- fp64 dense stages (csrc/dt_dense64.h)
+def _f32_rows(t, name, layouts):
+    """t, a float32 torch tensor of 2 or 3 dims (``layouts`` names them in the error); shape errors are ValueErrors."""
     if not isinstance(t, torch.Tensor):
         raise ValueError(f"{name} must be a torch tensor, got {type(t).__name__}")
-    if t.dim() == 2:
-        t = t.unsqueeze(1)
-    if t.dim() != 3:
-        raise ValueError(f"{name} must be [n, E] or step-major [n, P, E], got shape {tuple(t.shape)}")
+    if t.dim() not in (2, 3):
+        raise ValueError(f"{name} must be {layouts}, got shape {tuple(t.shape)}")
     if t.dtype != torch.float32:
         raise ValueError(f"{name} must be float32, got {t.dtype}")
     return t
 
 
+def _aligned_rows(t):
+    """t as the kernels read its rows (float4 loads): unit column stride, a 16-byte aligned base and every other stride a
+    multiple of 4 elements; a contiguous copy where it is not so"""
+    if t.stride(-1) != 1 or t.data_ptr() % 16 or any(s % 4 for s in t.stride()[:-1]):
+        return t.contiguous()
+    return t
+
+
+def _stage_events(events):
+    """the ``void *const *events`` argument of dt_pca_fit / dt_fid_distance: None, or the HIP events of the
+    torch.cuda.Event list (torch creates the HIP event at its first record)"""
+    if events is None:
+        return None
+    for e in events:
+        e.record()
+    return (c_void_p * len(events))(*[e._as_parameter_.value for e in events])
+
+
+# ---------------------------------------------------------------------- PCA (include/dt_hip_pca.h)
+PCA_MAX_K = 16
+
+
+def _pca_rows(t, name):
+    """[n, P, E] view of a step-major tensor (a 2-D [n, E] tensor is one problem)"""
+    t = _f32_rows(t, name, "[n, E] or step-major [n, P, E]")
+    return t.unsqueeze(1) if t.dim() == 2 else t
+
+
 def _pca_pad(t, E4):
     """t [n, P, E] as the kernel reads it: rows 16-byte aligned, E zero-padded to E4 (a PCA is blind to zero columns)."""
     E = t.shape[-1]
-    if E != E4:
-        return torch.nn.functional.pad(t, (0, E4 - E)).contiguous()
-    if t.stride(-1) != 1 or t.data_ptr() % 16 or t.stride(0) % 4 or t.stride(1) % 4:
-        return t.contiguous()
-    return t
+    return _aligned_rows(t) if E == E4 else torch.nn.functional.pad(t, (0, E4 - E)).contiguous()
 
 
 def _pca_check(a, b, k):
@@ -653,13 +672,9 @@ def device_pca(a, k, b=None, events=None):
     ws_bytes = lib.dt_pca_workspace_bytes(P, n, E4, k)
     if ws_bytes == 0:
         raise ValueError(f"dt_pca_workspace_bytes rejects P={P}, n={n}, E={E4}, k={k}")
-    ev = None
-    if events is not None:
-        if len(events) != 4:
-            raise ValueError("events must be 4 torch.cuda.Event")
-        for e in events:                 # torch creates the HIP event at its first record
-            e.record()
-        ev = (c_void_p * 4)(*[e._as_parameter_.value for e in events])
+    if events is not None and len(events) != 4:
+        raise ValueError("events must be 4 torch.cuda.Event")
+    ev = _stage_events(events)
     with torch.cuda.device(dev):
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         bs = (0, 0) if b is None else (b.stride(1), b.stride(0))
@@ -718,19 +733,8 @@ FID_MAX_ROWS = 32768
 FID_EVENTS = 5
 
 
-def _fid_set(t, name):
-    """[P, n, D] view of a feature set (a 2-D [n, D] tensor is one set); shape errors are ValueErrors."""
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{name} must be a torch tensor, got {type(t).__name__}")
-    if t.dim() not in (2, 3):
-        raise ValueError(f"{name} must be [n, D] or [P, n, D], got shape {tuple(t.shape)}")
-    if t.dtype != torch.float32:
-        raise ValueError(f"{name} must be float32, got {t.dtype}")
-    return t
-
-
 def _fid_check(a, b):
-    a, b = _fid_set(a, "a"), _fid_set(b, "b")
+    a, b = (_f32_rows(t, name, "[n, D] or [P, n, D]") for t, name in ((a, "a"), (b, "b")))
     if a.shape[-1] != b.shape[-1]:
         raise ValueError(f"b {tuple(b.shape)} does not match a {tuple(a.shape)}: both sets need the same feature width")
     if a.dim() == 3 and b.dim() == 3 and a.shape[0] != b.shape[0]:
@@ -753,8 +757,7 @@ def _fid_check(a, b):
 
 def _fid_rows(t):
     """(tensor, problem stride, row stride) as the kernel reads it: unit column stride, 16-byte aligned rows"""
-    if t.stride(-1) != 1 or t.data_ptr() % 16 or any(s % 4 or s < 0 for s in t.stride()[:-1]):
-        t = t.contiguous()
+    t = _aligned_rows(t)
     return t, (t.stride(0) if t.dim() == 3 else 0), t.stride(-2)
 
 
@@ -785,11 +788,7 @@ def device_fid(a, b, events=None, workspace=None):
     if ws_bytes == 0:
         raise ValueError(f"dt_fid_workspace_bytes rejects P={P}, n_a={n_a}, n_b={n_b}, D={D}")
     with torch.cuda.device(dev):
-        ev = None
-        if events is not None:
-            for e in events:                 # torch creates the HIP event at its first record
-                e.record()
-            ev = (c_void_p * FID_EVENTS)(*[e._as_parameter_.value for e in events])
+        ev = _stage_events(events)
         ws = workspace
         if ws is None:
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)

@@ -69,7 +69,11 @@ def test_fid_entry_host_code_clean_under_asan_and_ubsan():
     dict(n_a=2048, n_b=2048, P=1, D=2048),       # the largest side
     dict(n_a=1200, n_b=1000, P=1, D=2048),
     dict(n_a=300, n_b=257, P=2, D=64),           # more samples than features: rank capped by D
-], ids=["50x50", "50x50_P11_shared", "8x50_P3", "300x257_P2", "2x50", "2048x2048", "1200x1000", "D64_300x257_P2"])
+    dict(n_a=65, n_b=64, P=2, D=80),             # M^T M, one row of a into the second tile
+    dict(n_a=64, n_b=65, P=2, D=80),             # M M^T, one row of b into the second tile
+    dict(n_a=129, n_b=63, P=1, D=36),            # three tile rows of a; the last stage holds one quad
+], ids=["50x50", "50x50_P11_shared", "8x50_P3", "300x257_P2", "2x50", "2048x2048", "1200x1000", "D64_300x257_P2",
+        "D80_65x64_P2", "D80_64x65_P2", "D36_129x63"])
 def test_shapes_match_ref64(shape):
     n_a, n_b, P, D = shape["n_a"], shape["n_b"], shape["P"], shape["D"]
     a = feature_like(1000 + n_a, n_a, D)

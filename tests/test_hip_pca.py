@@ -80,7 +80,10 @@ def test_golden_pairs_match_ref64(golden):
     dict(nx=51, ny=0, E=768, P=2, k=3),          # a single set
     dict(nx=26, ny=26, E=675, P=2, k=16),        # 3 x 15 x 15: E padded to a multiple of 4
     dict(nx=2002, ny=0, E=768, P=1, k=3),        # T = 1000 at 16 x 16 x 3, one problem
-], ids=["default", "unequal", "mnist", "single", "pad", "n2002"])
+    dict(nx=33, ny=32, E=36, P=2, k=3),          # n = 65: one row into the second tile; the last stage holds one quad
+    dict(nx=65, ny=64, E=20, P=2, k=3),          # n = 129: three tile rows, mirrored off-diagonal tiles
+    dict(nx=64, ny=0, E=64, P=1, k=2),           # exactly one tile
+], ids=["default", "unequal", "mnist", "single", "pad", "n2002", "n65", "n129", "one_tile"])
 def test_shapes_match_ref64(shape):
     nx, ny, E, P, k = shape["nx"], shape["ny"], shape["E"], shape["P"], shape["k"]
     X = _walk(11 + nx, nx, P, E)

@@ -2,7 +2,8 @@
 device-only for gfx950 and reads the compiler's own resource remarks (nothing is run, no GPU needed).  Every
 conv_strip_bf16x6_kernel<BM, BN, KC, WK> with WK > 1 must report 0
 spilled VGPRs and 0 bytes of scratch: scratch traffic inside a K walk hides what the walk costs.
-The three conv code objects together hold exactly the 21 forms of csrc/dt_conv_forms.h."""
+The three conv code objects together hold exactly the 21 forms of csrc/dt_conv_forms.h.  No kernel of the fp64 dense
+stages (csrc/dt_pca.hip, csrc/dt_fid.hip) may spill either."""
 import functools
 import importlib.util
 import os
@@ -53,6 +54,19 @@ def test_k_split_strip_kernels_do_not_spill():
     assert forms == {(64, 128, 2, 2), (128, 64, 2, 2), (64, 64, 4, 4)}, forms
     bad = {n: (r["vgpr_spill"], r["scratch_bytes"]) for n, r in ksplit.items() if r["vgpr_spill"] or r["scratch_bytes"]}
     assert not bad, f"(spilled VGPRs, scratch bytes per lane): {bad}"
+
+
+@pytest.mark.skipif(not _have_hipcc(), reason="hipcc is not installed")
+def test_dense64_kernels_do_not_spill():
+    """every kernel of the two fp64 dense stages, the shared csrc/dt_dense64.h tile product and tridiagonalisation included"""
+    tiles = {"dt_pca.hip": {"pca_gram_kernel"}, "dt_fid.hip": {"fid_cross_kernel", "fid_square_kernel<0>", "fid_square_kernel<1>"}}
+    for src, tile_kernels in tiles.items():
+        res = _resources(src)
+        assert tile_kernels | {"tri_reflect_kernel", "tri_matvec_kernel", "tri_update_kernel"} <= set(res), sorted(res)
+        for name, r in sorted(res.items()):
+            print(f"{src} {name}: {r['vgprs']} VGPRs, {r['vgpr_spill']} spilled, {r['scratch_bytes']} B scratch")
+        bad = {n: (r["vgpr_spill"], r["scratch_bytes"]) for n, r in res.items() if r["vgpr_spill"] or r["scratch_bytes"]}
+        assert not bad, f"{src} (spilled VGPRs, scratch bytes per lane): {bad}"
 
 
 TILES = [(128, 128), (128, 64), (64, 128), (64, 64)]
