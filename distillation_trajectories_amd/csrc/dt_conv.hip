@@ -15,7 +15,9 @@
 // identically for A and B, so the sum over k is complete and the result layout is the standard one:
 // acc register r of lane l = D[row (r&3)+8*(r>>2)+4*(l>>5)][col l&31], i.e. a register is a 128-B run
 // of consecutive channels for two pixel rows -> coalesced NHWC stores.
-#include "dt_conv_epilogue.h"
+// The split-K slice arithmetic of the K walk, its chunk carry and the hand-over to the fused skip walk are KWalk of
+// dt_conv_walk.h, shared with dt_conv_bf16.hip; that header also says what of the walk stays spelled out here, and why.
+#include "dt_conv_walk.h"
 
 namespace dt {
 
@@ -35,7 +37,6 @@ __global__ __launch_bounds__(256, 4) void conv_gemm_kernel(const ConvParams p) {
   const int half = lane >> 5, l31 = lane & 31;
   const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
   const int HW = p.H * p.W;
-  const int CC = p.cin_p >> 4;                  // 16-channel chunks per tap
 
   // ---- per-thread staging coordinates (fixed for the whole K walk)
   int a_off[A_PER], a_off2[A_PER], a_y[A_PER], a_x[A_PER];
@@ -58,12 +59,7 @@ __global__ __launch_bounds__(256, 4) void conv_gemm_kernel(const ConvParams p) {
   const float *wbase = p.w + (size_t)n0 * 16 + tid * 4;
 
   f32x16 acc[MI][NI];
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+  DT_CLEAR_ACC(acc, MI, NI);
 
   // row / swizzle terms of this lane's fragment reads
   int a_row[MI], b_row[NI];
@@ -74,11 +70,10 @@ __global__ __launch_bounds__(256, 4) void conv_gemm_kernel(const ConvParams p) {
 
   // Software pipeline, one barrier per chunk: iteration `it` issues the global loads of chunk it+1
   // into registers, runs the MFMAs of chunk it from LDS stage it&1, then parks the registers in the
-  // other stage.  it == -1 is the prologue (loads chunk 0, no compute).
-  // split-K: grid.z slices the (tap, channel chunk) walk into equal runs of whole chunks
-  const int n_main = (p.tap_hi - p.tap_lo) * CC / p.splits;
-  const int n_iter = n_main + (p.in2 ? (p.cin2_p >> 4) : 0);   // main walk, then the fused 1x1 skip walk
-  int tap = p.tap_lo + (blockIdx.z * n_main) / CC, cc = (blockIdx.z * n_main) % CC;
+  // other stage.  it == -1 is the prologue (loads chunk 0, no compute).  The chunks are those of this
+  // split-K slice, then the fused 1x1 skip walk's (KWalk, dt_conv_walk.h).
+  KWalk k(p);
+  const int n_main = k.n_main, n_iter = k.n_iter;
   for (int it = -1; it < n_iter; ++it) {
     const bool more = it + 1 < n_iter;
     f32x4 ra[A_PER], rb[B_PER];
@@ -92,21 +87,21 @@ __global__ __launch_bounds__(256, 4) void conv_gemm_kernel(const ConvParams p) {
       for (int j = 0; j < B_PER; ++j) rb[j] = *reinterpret_cast<const f32x4 *>(wt + j * 1024);
     } else if (more) {
       int dy = 0, dx = 0;
-      if (p.ksize == 3) { dy = tap / 3 - 1; dx = tap - (tap / 3) * 3 - 1; }
-      const int shift = (dy * p.W + dx) * p.cin_p + cc * 16;
+      if (p.ksize == 3) { dy = k.tap / 3 - 1; dx = k.tap - (k.tap / 3) * 3 - 1; }
+      const int shift = (dy * p.W + dx) * p.cin_p + k.cc * 16;
 #pragma unroll
       for (int j = 0; j < A_PER; ++j) {
         const int yy = a_y[j] + dy, xx = a_x[j] + dx;
         const bool ok = a_ok[j] && yy >= 0 && yy < p.H && xx >= 0 && xx < p.W;
         ra[j] = ok ? *reinterpret_cast<const f32x4 *>(p.in + a_off[j] + shift) : f32x4{0.f, 0.f, 0.f, 0.f};
       }
-      const float *wt = wbase + (size_t)(tap * p.ccw + cc) * p.n_p * 16;
+      const float *wt = wbase + (size_t)(k.tap * p.ccw + k.cc) * p.n_p * 16;
 #pragma unroll
       for (int j = 0; j < B_PER; ++j) rb[j] = *reinterpret_cast<const f32x4 *>(wt + j * 1024);
-      if (++cc == CC) { cc = 0; ++tap; }
+      k.next();
     }
     if (it >= 0) {
-      if (it == n_main && p.in2) conv_midpoint<MI, NI>(p, acc, n0, wn, l31);
+      if (k.at_midpoint(p, it)) conv_midpoint<MI, NI>(p, acc, n0, wn, l31);
       const float *A = lds + (it & 1) * STAGE, *B = A + BM * 16;
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
@@ -294,7 +289,7 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(const ConvParams p
 template <bool POOL>
 static int launch_splitk_epilogue_t(const ConvParams &p, hipStream_t s) {
   const size_t total = (size_t)(POOL ? p.M / 4 : p.M) * (p.cout_p / 4);
-  const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+  const int blocks = grid_blocks(total, 4096);
   ProfileScope prof(KC_SPLITK_EPILOGUE, 0.0, 4.0 * p.M * p.cout_p * (p.splits + 1.0 + (POOL ? 0.25 : 0.0)), s);
   switch (p.splits) {
     case 2: splitk_epilogue_kernel<2, POOL><<<blocks, 256, 0, s>>>(p); break;
@@ -315,8 +310,7 @@ int launch_splitk_epilogue(const ConvParams &p, hipStream_t s) {
 // ---------------------------------------------------------------------------------------------
 // Weight re-tiling (runs once per model in dt_unet_create).
 // wp[((kc*n_p + n)*16) + 4*(slot ^ ((n>>2)&3)) + e] = W[n][c(k)][tap(k)],  k = kc*16 + 4*slot + e,
-// k = tap*cin_p + cp; padded input channel cp maps to real channel c through the concat split
-// (channels [0,split_c) live at [0,split_c) and channels [split_c,cin) at [split_cp, ...)).
+// k = tap*cin_p + cp; padded input channel cp maps to real channel c through the concat split (conv_real_channel).
 __global__ void pack_conv_kernel(const float *__restrict__ w, float *__restrict__ wp, int cout, int cin, int ksize,
                                  int cin_p, int n_p, int split_c, int split_cp, size_t total) {
   for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
@@ -328,9 +322,7 @@ __global__ void pack_conv_kernel(const float *__restrict__ w, float *__restrict_
     const int lslot = pslot ^ ((n >> 2) & 3);
     const int k = kc * 16 + lslot * 4 + e;
     const int tap = k / cin_p, cp = k - tap * cin_p;
-    int c = -1;
-    if (cp < split_cp) { if (cp < split_c) c = cp; }
-    else { const int cc = split_c + (cp - split_cp); if (cc < cin) c = cc; }
+    const int c = conv_real_channel(cp, cin, cin_p, split_c, split_cp);
     float v = 0.f;
     if (n < cout && c >= 0) v = w[((size_t)n * cin + c) * (ksize * ksize) + tap];
     wp[idx] = v;
@@ -340,7 +332,7 @@ __global__ void pack_conv_kernel(const float *__restrict__ w, float *__restrict_
 int launch_pack_conv(const float *w, float *wp, int cout, int cin, int ksize, int cin_p, int n_p, int split_c,
                      int split_cp, hipStream_t s) {
   const size_t total = (size_t)ksize * ksize * cin_p * n_p;
-  const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+  const int blocks = grid_blocks(total, 4096);
   pack_conv_kernel<<<blocks, 256, 0, s>>>(w, wp, cout, cin, ksize, cin_p, n_p, split_c, split_cp, total);
   DT_LAUNCH_CHECK();
   return DT_OK;

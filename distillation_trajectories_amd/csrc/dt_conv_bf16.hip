@@ -14,10 +14,10 @@
 //
 // Weights are split once at pack time ([K/16][3 planes][N_pad][16 k], LDS-ready).  Activations stay fp32
 // in HBM; a thread splits the 8 consecutive k it stages (2 x dwordx4 -> 3 x ds_write_b128, ~45 VALU).
-// Tiling, tap walk, split-K and epilogue are those of dt_conv.hip.  LDS: per stage 3 planes x (BM+BN) rows
-// x 32 B; the two 16-B halves of a row are swapped on rows with bit 3 set, which makes ds_read_b128's
-// 16-lane groups conflict-free (rows 32 B apart would otherwise collide two-way).
-#include "dt_conv_epilogue.h"
+// Tiling, tap walk, split-K and epilogue are those of dt_conv.hip (the walk's slice arithmetic: KWalk, dt_conv_walk.h).
+// LDS: per stage 3 planes x (BM+BN) rows x 32 B; the two 16-B halves of a row are swapped on rows with bit 3 set, which
+// makes ds_read_b128's 16-lane groups conflict-free (rows 32 B apart would otherwise collide two-way).
+#include "dt_conv_walk.h"
 
 namespace dt {
 
@@ -39,7 +39,6 @@ __global__ __launch_bounds__(256, BM * BN > 128 * 128 ? 2 : 3) void conv_gemm_bf
   const int half = lane >> 5, l31 = lane & 31;
   const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
   const int HW = p.H * p.W;
-  const int CC = p.cin_p >> 4;
 
   // ---- A staging: item -> (row, k-half): 8 consecutive k = 32 contiguous bytes of one pixel; AP items per thread
   constexpr int NT = 64 * WM * WN;
@@ -64,12 +63,7 @@ __global__ __launch_bounds__(256, BM * BN > 128 * 128 ? 2 : 3) void conv_gemm_bf
   const size_t w_plane = (size_t)p.n_p * 16;                       // elements between planes of one chunk
 
   f32x16 acc[MI][NI];
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+  DT_CLEAR_ACC(acc, MI, NI);
 
   int a_frag[MI], b_frag[NI];
 #pragma unroll
@@ -83,10 +77,9 @@ __global__ __launch_bounds__(256, BM * BN > 128 * 128 ? 2 : 3) void conv_gemm_bf
     b_frag[ni] = row * 16 + ((half ^ ((row >> 3) & 1)) << 3);
   }
 
-  // split-K: grid.z slices the (tap, channel chunk) walk into equal runs of whole chunks
-  const int n_main = (p.tap_hi - p.tap_lo) * CC / p.splits;
-  const int n_iter = n_main + (p.in2 ? (p.cin2_p >> 4) : 0);       // main walk, then the fused 1x1 skip walk
-  int tap = p.tap_lo + (blockIdx.z * n_main) / CC, cc = (blockIdx.z * n_main) % CC;
+  // the walk's pipeline, over the chunks of this split-K slice and then the fused 1x1 skip walk's (KWalk, dt_conv_walk.h)
+  KWalk k(p);
+  const int n_main = k.n_main, n_iter = k.n_iter;
   for (int it = -1; it < n_iter; ++it) {
     const bool more = it + 1 < n_iter;
     f32x4 ra0[AP], ra1[AP];
@@ -111,27 +104,27 @@ __global__ __launch_bounds__(256, BM * BN > 128 * 128 ? 2 : 3) void conv_gemm_bf
         }
     } else if (more) {
       int dy = 0, dx = 0;
-      if (p.ksize == 3) { dy = tap / 3 - 1; dx = tap - (tap / 3) * 3 - 1; }
+      if (p.ksize == 3) { dy = k.tap / 3 - 1; dx = k.tap - (k.tap / 3) * 3 - 1; }
 #pragma unroll
       for (int i = 0; i < AP; ++i) {
         const int yy = a_y[i] + dy, xx = a_x[i] + dx;
         if (a_ok[i] && yy >= 0 && yy < p.H && xx >= 0 && xx < p.W) {
-          const float *src = p.in + a_off[i] + (dy * p.W + dx) * p.cin_p + cc * 16;
+          const float *src = p.in + a_off[i] + (dy * p.W + dx) * p.cin_p + k.cc * 16;
           ra0[i] = *reinterpret_cast<const f32x4 *>(src);
           ra1[i] = *reinterpret_cast<const f32x4 *>(src + 4);
         }
       }
-      const __bf16 *wt = wbase + (size_t)(tap * p.ccw + cc) * 3 * w_plane;
+      const __bf16 *wt = wbase + (size_t)(k.tap * p.ccw + k.cc) * 3 * w_plane;
 #pragma unroll
       for (int i = 0; i < BP; ++i)
         if (tid + i * NT < BN * 2) {
 #pragma unroll
           for (int pl = 0; pl < 3; ++pl) rb[i][pl] = *reinterpret_cast<const u32x4 *>(wt + i * NT * 8 + pl * w_plane);
         }
-      if (++cc == CC) { cc = 0; ++tap; }
+      k.next();
     }
     if (it >= 0) {
-      if (it == n_main && p.in2) conv_midpoint<MI, NI>(p, acc, n0, wn, l31);
+      if (k.at_midpoint(p, it)) conv_midpoint<MI, NI>(p, acc, n0, wn, l31);
       const __bf16 *A = lds + (it & 1) * STAGE, *B = A + 3 * PLANE_A;
       bf16x8 fb[NI][3];
 #pragma unroll
@@ -197,9 +190,7 @@ __global__ void pack_conv_bf16x3_kernel(const float *__restrict__ w, __bf16 *__r
     const int hh = phh ^ ((n >> 3) & 1);
     const int k = (int)kc * 16 + hh * 8 + j;
     const int tap = k / cin_w, cp = k - tap * cin_w;       // (channels [cin_p, cin_w) of a tap: zero chunks, see ConvParams::ccw)
-    int c = -1;
-    if (cp < split_cp) { if (cp < split_c) c = cp; }
-    else if (cp < cin_p) { const int cc = split_c + (cp - split_cp); if (cc < cin) c = cc; }
+    const int c = conv_real_channel(cp, cin, cin_p, split_c, split_cp);
     float v = 0.f;
     if (n < cout && c >= 0) v = w[((size_t)n * cin + c) * (ksize * ksize) + tap];
     const __bf16 a1 = (__bf16)v;
@@ -216,7 +207,7 @@ int launch_pack_conv_bf16x3(const float *w, void *wp, int cout, int cin, int ksi
                             int split_cp, hipStream_t s) {
   if (cin_w < cin_p || cin_w % 16) return DT_E_ARG;
   const size_t total = (size_t)ksize * ksize * cin_w * n_p;
-  const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+  const int blocks = grid_blocks(total, 4096);
   pack_conv_bf16x3_kernel<<<blocks, 256, 0, s>>>(w, reinterpret_cast<__bf16 *>(wp), cout, cin, ksize, cin_p, cin_w, n_p,
                                                  split_c, split_cp, total);
   DT_LAUNCH_CHECK();

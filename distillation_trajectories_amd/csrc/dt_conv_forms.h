@@ -24,6 +24,14 @@ constexpr bool is_strip(int kind) { return kind >= KIND_STRIP; }
 // zero rows anyway, so W rows are enough -- which is what lets the K = 32 tile fit twice per CU at W = 16.
 constexpr int strip_halo(int W, int bm) { return bm % W == 0 ? W : W + 1; }
 
+// The padded-channel map of every weight pack: the real input channel behind padded channel cp of a tap, or -1 where cp is
+// padding.  The activations' channels are padded to 16 per tensor and a decoder block reads the concat of two tensors, so
+// real channels [0, split_c) live at [0, split_c) and real channels [split_c, cin) from split_cp on (split_c == cin,
+// split_cp == cin_p without a concat); the zero chunks [cin_p, cin_w) of a split-bf16 pack (ConvParams::ccw) are padding too.
+constexpr int conv_real_channel(int cp, int cin, int cin_p, int split_c, int split_cp) {
+  return cp < split_cp ? (cp < split_c ? cp : -1) : (cp < cin_p && split_c + (cp - split_cp) < cin ? split_c + (cp - split_cp) : -1);
+}
+
 // Profiler classes of the convolution launches (KernelClass, dt_internal.h, continues the numbering).  The benchmark groups
 // kernels by their printed names: their number and order are fixed.
 enum ConvClass {

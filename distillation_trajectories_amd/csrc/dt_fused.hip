@@ -520,7 +520,7 @@ __global__ __launch_bounds__(kThreads, 4) void unet_fused_kernel(const FusedArgs
 
 // OIHW conv weights -> [tap][chunk][channel tile][lane][4]: lane (i = l & 15, s = l >> 4) holds input channels
 // chunk * 16 + 4 s .. + 3 of output channel tile * 16 + i; the padded input channels follow the activations' layout
-// ([0, split_cp) <-> real [0, split_c), the rest <-> real [split_c, cin): the decoder's concat of two padded tensors)
+// (conv_real_channel: the decoder's concat of two padded tensors)
 __global__ void pack_fused_conv_kernel(const float *__restrict__ w, float *__restrict__ dst, int cout, int cin, int taps, int kc,
                                        int ot, int split_c, int split_cp) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -530,9 +530,7 @@ __global__ void pack_fused_conv_kernel(const float *__restrict__ w, float *__res
   const int o_t = t % ot; t /= ot;
   const int k_c = t % kc, tap = t / kc;
   const int oc = o_t * 16 + (lane & 15), cp = k_c * 16 + 4 * (lane >> 4) + j;
-  int ci;
-  if (cp < split_cp) ci = cp < split_c ? cp : -1;
-  else ci = cp - split_cp + split_c < cin ? cp - split_cp + split_c : -1;
+  const int ci = conv_real_channel(cp, cin, kc * 16, split_c, split_cp);
   dst[idx] = (oc < cout && ci >= 0) ? w[((size_t)oc * cin + ci) * taps + tap] : 0.f;
 }
 

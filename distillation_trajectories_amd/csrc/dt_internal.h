@@ -58,6 +58,8 @@ constexpr int kBlocks = 8;
 constexpr int kChunkPad = 4;   // chunk granularity of the split-bf16 weight packs (see ConvParams::ccw)
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+// 256-thread blocks of a grid-stride launch over `total` items, at most `cap` (each launcher's own)
+inline int grid_blocks(size_t total, int cap) { return (int)((total + 255) / 256 < (size_t)cap ? (total + 255) / 256 : (size_t)cap); }
 // whether a walk of `cc` chunks in groups of `div` (K chunks per step x split-K slices) stays inside a pack of `ccw` chunks
 inline bool chunks_fit(int cc, int ccw, int div) { return div >= 1 && round_up(cc, div) <= ccw; }
 // 16-channel weight chunks per tap of a split-bf16 pack of cin_p input channels (zero chunks up to a multiple of kChunkPad)

@@ -133,7 +133,7 @@ __global__ void maxpool_kernel(const float4 *__restrict__ in, float4 *__restrict
 
 int launch_maxpool(const float *in, float *out, int Bt, int H, int W, int cp, hipStream_t s) {
   const size_t total = (size_t)Bt * (H / 2) * (W / 2) * (cp / 4);
-  const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+  const int blocks = grid_blocks(total, 2048);
   ProfileScope prof(KC_POOL, 0.0, 4.0 * Bt * H * W * cp * 1.25, s);
   maxpool_kernel<<<blocks, 256, 0, s>>>(reinterpret_cast<const float4 *>(in), reinterpret_cast<float4 *>(out), Bt,
                                          H, W, cp / 4);
@@ -176,7 +176,7 @@ int launch_upcat(const float *lo, const float *skip, float *out, int Bt, int h, 
                  hipStream_t s) {
   const size_t total = (size_t)Bt * 4 * h * w * ((c1p + (skip ? c2p : 0)) / 4);
   if (total >= (1ull << 32)) return DT_E_SHAPE;
-  const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+  const int blocks = grid_blocks(total, 8192);
   ProfileScope prof(KC_UPCAT, 0.0, 4.0 * Bt * h * w * (c1p + 4.0 * c1p + (skip ? 8.0 * c2p : 0.0)), s);
   upcat_kernel<<<blocks, 256, 0, s>>>(reinterpret_cast<const float4 *>(lo), reinterpret_cast<const float4 *>(skip),
                                        reinterpret_cast<float4 *>(out), Bt, h, w, c1p / 4, c2p / 4);
@@ -292,7 +292,7 @@ extern "C" int dt_resize_bilinear(const float *in, float *out, int planes, int h
   if (!in || !out) return DT_E_NULL;
   if (planes < 1 || h < 1 || w < 1 || H < 1 || W < 1) return DT_E_SHAPE;
   const size_t total = (size_t)planes * H * ((W + 3) / 4);
-  const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+  const int blocks = grid_blocks(total, 4096);
   ProfileScope prof(KC_POOL, 0.0, 4.0 * planes * ((double)h * w + (double)H * W), s);
   resize_bilinear_kernel<<<blocks, 256, 0, s>>>(in, out, planes, h, w, H, W);
   DT_LAUNCH_CHECK();
@@ -313,7 +313,7 @@ int launch_head(const float *lo, const float *wf, const float *bias, float *lowr
 int launch_head_upsample(const float *lowres, float *eps, int Bt, int h, int w, int C, hipStream_t s) {
   const size_t n_pix = (size_t)Bt * h * w;
   const size_t total = n_pix * 4 * C;
-  const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+  const int blocks = grid_blocks(total, 2048);
   ProfileScope prof(KC_HEAD_UP, 0.0, 4.0 * n_pix * (4.0 + 4.0 * C), s);
   head_upsample_kernel<<<blocks, 256, 0, s>>>(lowres, eps, Bt, h, w, C);
   DT_LAUNCH_CHECK();

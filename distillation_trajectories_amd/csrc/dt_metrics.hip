@@ -144,7 +144,7 @@ extern "C" int dt_traj_sample_mean(const float *traj, int n, int B, int E, float
   if (!traj || !out) return DT_E_NULL;
   if (n < 1 || B < 1 || E < 1) return DT_E_SHAPE;
   const size_t total = (size_t)n * E;
-  const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+  const int blocks = grid_blocks(total, 2048);
   ProfileScope prof(KC_METRICS, 0.0, 4.0 * total * (B + 1.0), s);
   sample_mean_kernel<<<blocks, 256, 0, s>>>(traj, B, E, out, total);
   DT_LAUNCH_CHECK();

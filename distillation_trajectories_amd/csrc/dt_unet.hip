@@ -78,15 +78,24 @@ ProfileScope::~ProfileScope() {
 }
 }  // namespace dt
 
+// One convolution of a block, under its slot: 0 = the 1x1 skip, 1 = conv1 (both over the block input), 2 = conv2 (over
+// conv1's output) -- the key of ResolvedForward::c, has_launch, conv_layer and every plan hook.
+struct ConvW {
+  int cin, cin_p;         // real / padded input channels
+  int split_c, split_cp;  // concat split of the input channels (== cin, cin_p when no concat)
+  int cin_w;              // input channels per tap of the split-bf16 pack: cin_p padded to kChunkPad chunks
+  int ksize;              // 1 or 3
+  float *w, *wb;          // packed weights: fp32 tiles (dt_conv.hip), three bf16 planes (dt_conv_bf16.hip); nullptr: no such launch
+  float *scale, *shift;   // folded BN (a plain conv: 1 and its bias); nullptr: no such conv
+};
+constexpr int kSlotWeight[3] = {DT_BT_RES_W, DT_BT_CONV1_W, DT_BT_CONV2_W};   // a slot's OIHW weights among a block's tensors
+
 struct BlockW {
   int cin, cout;          // real channels
   int cin_p, cout_p, n_p; // padded
-  int split_c, split_cp;  // concat split of the input channels (== cin, cin_p when no concat)
-  int cin_w, cout_w;      // input channels per tap of the split-bf16 packs of conv1 (and the skip) / conv2: cin_p / cout_p padded to kChunkPad chunks
+  int split_c, split_cp;  // concat split of the block input
   bool has_res;
-  float *w1, *w2, *wr;    // packed conv weights (fp32 tiles)
-  float *w1b, *w2b, *wrb; // the same weights split into three bf16 planes (dt_conv_bf16.hip)
-  float *s1, *h1, *s2, *h2, *sr, *hr;  // scale/shift per conv
+  ConvW c[3];             // enc1: c[1].w is the direct first-layer kernel's pack, c[0] is empty (w3 instead)
   float *w3;              // enc1 only: skip weights for the in-epilogue 1x1 (n_p x 4)
   int tb_off;             // channel offset of this block in a time-bias row
 };
@@ -232,7 +241,7 @@ ConvLayer conv_layer(const dt_unet *u, const ResolvedForward &f, int j, int slot
   const int h = f.shape.H / kDiv[j], w = f.shape.W / kDiv[j];
   const int M = (j == 0 && f.shared_enc1 ? f.shape.imgs : f.shape.Bt) * h * w;
   const int taps = slot == 0 || (h == 1 && w == 1) ? 1 : 9;   // a 1x1 image only ever sees the centre tap of a padded 3x3 kernel
-  return ConvLayer{M, w, k.n_p, slot == 2 ? k.cout_p : k.cin_p, taps, j > 0 && M <= kSplitMaxRows, slot == 2 && j > 0 && k.has_res};
+  return ConvLayer{M, w, k.n_p, k.c[slot].cin_p, taps, j > 0 && M <= kSplitMaxRows, slot == 2 && j > 0 && k.has_res};
 }
 
 ResolvedForward resolve_forward(const dt_unet *u, const FwdShape &sh, const TunedShape *tuned) {
@@ -264,24 +273,26 @@ ResolvedForward resolve_forward(const dt_unet *u, const FwdShape &sh, const Tune
 ConvParams bind_conv(const dt_unet *u, const ResolvedForward &f, int j, int slot, const ConvChoice &c, const float *in, float *ws,
                      const Plan &pl, const float *tb, int tb_div) {
   const BlockW &k = u->blk[j];
+  const ConvW &cw = k.c[slot];
   const ConvLayer L = conv_layer(u, f, j, slot);
   const int h = pl.H[j], w = pl.W[j];
   ConvParams p{};
   p.M = L.M; p.H = h; p.W = w;
   p.cin_p = L.cin_p; p.cout_p = k.cout_p; p.n_p = k.n_p;
-  p.cin_real = slot == 2 ? k.cout : k.cin; p.cout_real = k.cout;
+  p.cin_real = cw.cin; p.cout_real = k.cout;
   p.tb_stride = u->tb_stride; p.m_per_tb = h * w * tb_div;
   p.slab = ws + pl.slab;
   p.in = slot == 2 ? ws + pl.h[j] : in;
-  p.ksize = slot == 0 ? 1 : 3;
+  p.ksize = cw.ksize;
+  p.scale = cw.scale; p.shift = cw.shift;
   p.tap_lo = slot > 0 && L.taps == 1 ? 4 : 0; p.tap_hi = p.tap_lo + L.taps;
   p.relu = slot > 0;
   if (slot == 0) {
-    p.scale = k.sr; p.shift = k.hr; p.out = ws + pl.r[j];
+    p.out = ws + pl.r[j];
   } else if (slot == 1) {
-    p.scale = k.s1; p.shift = k.h1; p.tb = tb + k.tb_off; p.out = ws + pl.h[j];
+    p.tb = tb + k.tb_off; p.out = ws + pl.h[j];
   } else {
-    p.scale = k.s2; p.shift = k.h2; p.out = ws + pl.o[j];
+    p.out = ws + pl.o[j];
     if (f.pool_fused[j]) p.pool_out = ws + pl.pool[j];
     if (j == 0) {
       // the C-channel skip of enc1 is recomputed in the epilogue from the patches' centre taps (k = 9c+4)
@@ -301,12 +312,13 @@ ConvParams bind_conv(const dt_unet *u, const ResolvedForward &f, int j, int slot
   // the choice: tile, kind, the weight pack of the kind (and its chunk width), the folded skip walk where c folds it
   const bool fp32 = c.kind == KIND_FP32;
   p.bm = c.bm; p.bn = c.bn; p.splits = c.splits; p.kind = c.kind;
-  p.w = slot == 0 ? (fp32 ? k.wr : k.wrb) : (slot == 1 ? (fp32 ? k.w1 : k.w1b) : (fp32 ? k.w2 : k.w2b));
-  p.ccw = fp32 ? p.cin_p >> 4 : pack_chunks(p.cin_p);
-  if (c.fuse) {   // conv2 with the block's 1x1 skip folded into its K walk (the slot-0 launch is then skipped)
+  p.w = fp32 ? cw.w : cw.wb;
+  p.ccw = (fp32 ? cw.cin_p : cw.cin_w) >> 4;
+  if (c.fuse) {   // conv2 with the block's 1x1 skip (slot 0) folded into its K walk (the slot-0 launch is then skipped)
+    const ConvW &sk = k.c[0];
     p.add = nullptr;
-    p.in2 = in; p.w2 = fp32 ? k.wr : k.wrb; p.bias2 = k.hr; p.cin2_p = k.cin_p; p.cin2_real = k.cin;
-    p.ccw2 = fp32 ? k.cin_p >> 4 : k.cin_w >> 4;
+    p.in2 = in; p.w2 = fp32 ? sk.w : sk.wb; p.bias2 = sk.shift; p.cin2_p = sk.cin_p; p.cin2_real = sk.cin;
+    p.ccw2 = (fp32 ? sk.cin_p : sk.cin_w) >> 4;
   }
   return p;
 }
@@ -317,7 +329,7 @@ int run_block(const dt_unet *u, const ResolvedForward &f, int j, const float *in
     const BlockW &k = u->blk[0];
     if (!f.shared_enc1 && f.shape.single) return DT_E_ARG;   // mixed batches exist in the shared-enc1 formulation only
     // (shared: the passes' time biases enter in conv2's epilogue)
-    const int st = launch_first_conv(in, k.w1, k.s1, k.h1, f.shared_enc1 ? nullptr : tb + k.tb_off, u->tb_stride, tb_div, ws + pl.h[0],
+    const int st = launch_first_conv(in, k.c[1].w, k.c[1].scale, k.c[1].shift, f.shared_enc1 ? nullptr : tb + k.tb_off, u->tb_stride, tb_div, ws + pl.h[0],
                                      f.shape.imgs, f.shared_enc1 ? 1 : f.shape.Bt / f.shape.imgs, u->desc.channels, pl.H[0], pl.W[0], k.cout, k.cout_p, s);
     if (st) return st;
   }
@@ -398,13 +410,12 @@ int build_fused(dt_unet *u, const float *const *bt, hipStream_t s) {
   Bump bump;
   const int tb_cols = 2 * c0p + 6 * c1p;
   const size_t o_par = bump.take((size_t)5 * tb_cols + 4 * c0p);
-  size_t o1[kBlocks] = {}, o2[kBlocks] = {}, orr[kBlocks] = {};
-  for (int j = 0; j < kBlocks; ++j) {
-    const BlockW &k = u->blk[j];
-    if (j > 0) o1[j] = bump.take((size_t)9 * k.cin_p * k.cout_p);
-    o2[j] = bump.take((size_t)9 * k.cout_p * k.cout_p);
-    if (k.has_res && j > 0) orr[j] = bump.take((size_t)k.cin_p * k.cout_p);
-  }
+  size_t o_w[kBlocks][3] = {};
+  for (int j = 0; j < kBlocks; ++j)
+    for (int slot = 0; slot < 3; ++slot) {
+      const ConvW &c = u->blk[j].c[slot];
+      if (has_launch(u, j, slot)) o_w[j][slot] = bump.take((size_t)c.ksize * c.ksize * c.cin_p * u->blk[j].cout_p);
+    }
   const size_t o_wf = bump.take((size_t)2 * (c0p / 16) * 256);
   const size_t o_ops = bump.take((sizeof(FusedOp) * kFusedMaxOps + 3) / 4);
   if (bump.off >= (1u << 30)) return DT_OK;                     // offsets are ints
@@ -428,17 +439,21 @@ int build_fused(dt_unet *u, const float *const *bt, hipStream_t s) {
     const float *const *t = bt + j * DT_BT_COUNT;
     FusedBlockW &f = m.blk[j];
     const int cp = k.cout_p;
-    d2d(o_par + pj, k.s1, cp); d2d(o_par + pj + cp, k.h1, cp); d2d(o_par + pj + 2 * cp, k.s2, cp); d2d(o_par + pj + 3 * cp, k.h2, cp);
-    if (k.has_res && j > 0) d2d(o_par + pj + 4 * cp, k.hr, cp);
     f.tb_off = k.tb_off;
-    f.c1 = FusedConvW{(int)o1[j], pj, pj + cp};
-    f.c2 = FusedConvW{(int)o2[j], pj + 2 * cp, pj + 3 * cp};
-    f.cr = FusedConvW{(int)orr[j], 0, pj + 4 * cp};
+    // the block's five vectors in the parameter block: conv1's scale and shift, conv2's, the skip conv's bias
+    FusedConvW *const fc[3] = {&f.cr, &f.c1, &f.c2};
+    const int at_scale[3] = {-1, 0, 2}, at_shift[3] = {4, 1, 3};
+    for (int slot = 0; slot < 3 && st == DT_OK; ++slot) {
+      const ConvW &c = k.c[slot];
+      const int scale = slot ? pj + at_scale[slot] * cp : 0, shift = pj + at_shift[slot] * cp;
+      if (slot && c.scale) d2d(o_par + scale, c.scale, cp);
+      if (c.shift) d2d(o_par + shift, c.shift, cp);
+      *fc[slot] = FusedConvW{(int)o_w[j][slot], scale, shift};
+      if (st == DT_OK && has_launch(u, j, slot))
+        st = launch_pack_fused_conv(t[kSlotWeight[slot]], F + o_w[j][slot], k.cout, c.cin, c.ksize * c.ksize, c.cin_p / 16, k.cout_p / 16,
+                                    c.split_c, c.split_cp, s);
+    }
     pj += 5 * cp;
-    if (j > 0) st = launch_pack_fused_conv(t[DT_BT_CONV1_W], F + o1[j], k.cout, k.cin, 9, k.cin_p / 16, k.cout_p / 16, k.split_c, k.split_cp, s);
-    if (!st) st = launch_pack_fused_conv(t[DT_BT_CONV2_W], F + o2[j], k.cout, k.cout, 9, k.cout_p / 16, k.cout_p / 16, k.cout, k.cout_p, s);
-    if (!st && k.has_res && j > 0)
-      st = launch_pack_fused_conv(t[DT_BT_RES_W], F + orr[j], k.cout, k.cin, 1, k.cin_p / 16, k.cout_p / 16, k.split_c, k.split_cp, s);
   }
   if (st == DT_OK && hipMemsetAsync(F + o_par + 4 * c0p, 0, sizeof(float) * c0p, s) != hipSuccess) st = (int)hipGetLastError();   // (enc1 has no skip-conv bias)
   u->fused_par = (int)o_par; u->fused_n_par = 5 * tb_cols + 4 * c0p;
@@ -539,8 +554,8 @@ int dt_unet_create(const dt_unet_desc *desc, const float *const *bt, const float
   const int cout[kBlocks] = {d[0], d[1], d[2], d[3], d[3], d[2], d[1], d[0]};
   const int up_c[kBlocks] = {0, 0, 0, 0, 0, d[3], d[2], d[1]};   // channels coming from the upsampled branch
   Bump bump;
-  size_t o_w1[kBlocks], o_w2[kBlocks], o_wr[kBlocks], o_ss[kBlocks];
-  size_t o_w1b[kBlocks], o_w2b[kBlocks], o_wrb[kBlocks];   // bf16x3 packs: 6 bytes per weight = 1.5 floats
+  struct { size_t w, wb, ss; } o_c[kBlocks][3] = {};   // a slot's fp32 pack, bf16x3 pack, scale + shift
+  size_t o_w3 = 0;
   int tb = 0;
   for (int j = 0; j < kBlocks; ++j) {
     BlockW &k = u->blk[j];
@@ -555,18 +570,26 @@ int dt_unet_create(const dt_unet_desc *desc, const float *const *bt, const float
       k.split_c = cin[j]; k.split_cp = k.cin_p;
     }
     k.has_res = cin[j] != cout[j];
-    k.cin_w = round_up(k.cin_p, 16 * kChunkPad); k.cout_w = round_up(k.cout_p, 16 * kChunkPad);
     for (int t = 0; t < DT_BT_COUNT; ++t) {
       const bool optional = t == DT_BT_RES_W || t == DT_BT_RES_B;
       if (!bt[j * DT_BT_COUNT + t] && (!optional || k.has_res)) { delete u; return DT_E_NULL; }
     }
-    o_w1[j] = bump.take(j == 0 ? (size_t)9 * C * k.cout_p : (size_t)9 * k.cin_p * k.n_p);   // enc1: wf[9C][cout_p]
-    o_w2[j] = bump.take((size_t)9 * k.cout_p * k.n_p);
-    o_wr[j] = k.has_res ? bump.take(j == 0 ? (size_t)4 * k.n_p : (size_t)k.cin_p * k.n_p) : 0;
-    o_ss[j] = bump.take((size_t)6 * k.n_p);
-    o_w1b[j] = j == 0 ? 0 : bump.take((size_t)9 * k.cin_w * k.n_p * 3 / 2);
-    o_w2b[j] = bump.take((size_t)9 * k.cout_w * k.n_p * 3 / 2);
-    o_wrb[j] = (k.has_res && j > 0) ? bump.take((size_t)k.cin_w * k.n_p * 3 / 2) : 0;
+    for (int slot = 0; slot < 3; ++slot) {
+      ConvW &c = k.c[slot];
+      c = slot == 2 ? ConvW{k.cout, k.cout_p, k.cout, k.cout_p} : ConvW{k.cin, k.cin_p, k.split_c, k.split_cp};
+      c.cin_w = pack_chunks(c.cin_p) * 16;
+      c.ksize = slot == 0 ? 1 : 3;
+      const size_t taps = (size_t)c.ksize * c.ksize;
+      if (has_launch(u, j, slot)) {   // a tile-GEMM / strip launch of its own: both packs (bf16x3: 6 bytes per weight = 1.5 floats)
+        o_c[j][slot].w = bump.take(taps * c.cin_p * k.n_p);
+        o_c[j][slot].wb = bump.take(taps * c.cin_w * k.n_p * 3 / 2);
+      }
+      if (has_launch(u, j, slot) || slot == 1) o_c[j][slot].ss = bump.take((size_t)2 * k.n_p);
+    }
+    if (j == 0) {   // enc1: conv1 is the direct first-layer kernel over wf[9C][cout_p]; the skip is w3[n_p][4] in conv2's epilogue
+      o_c[0][1].w = bump.take((size_t)9 * C * k.cout_p);
+      if (k.has_res) o_w3 = bump.take((size_t)4 * k.n_p);
+    }
     k.tb_off = tb;
     tb += k.cout_p;
   }
@@ -594,31 +617,29 @@ int dt_unet_create(const dt_unet_desc *desc, const float *const *bt, const float
   for (int j = 0; j < kBlocks && st == DT_OK; ++j) {
     BlockW &k = u->blk[j];
     const float *const *t = bt + j * DT_BT_COUNT;
-    k.w1 = S + o_w1[j]; k.w2 = S + o_w2[j];
-    k.wr = (k.has_res && j > 0) ? S + o_wr[j] : nullptr;
-    k.w3 = j == 0 ? S + o_wr[j] : nullptr;
-    k.w1b = S + o_w1b[j]; k.w2b = S + o_w2b[j]; k.wrb = (k.has_res && j > 0) ? S + o_wrb[j] : nullptr;
-    float *ss = S + o_ss[j];
-    k.s1 = ss; k.h1 = ss + k.n_p; k.s2 = ss + 2 * k.n_p; k.h2 = ss + 3 * k.n_p; k.sr = ss + 4 * k.n_p; k.hr = ss + 5 * k.n_p;
-    if (j == 0)
-      st = launch_pack_first_conv(t[DT_BT_CONV1_W], k.w1, k.cout, C, k.cout_p, s);
-    else
-      st = launch_pack_conv(t[DT_BT_CONV1_W], k.w1, k.cout, k.cin, 3, k.cin_p, k.n_p, k.split_c, k.split_cp, s);
-    if (!st) st = launch_pack_conv(t[DT_BT_CONV2_W], k.w2, k.cout, k.cout, 3, k.cout_p, k.n_p, k.cout, k.cout_p, s);
-    if (!st && k.has_res && j > 0)
-      st = launch_pack_conv(t[DT_BT_RES_W], k.wr, k.cout, k.cin, 1, k.cin_p, k.n_p, k.split_c, k.split_cp, s);
-    if (!st && j > 0) st = launch_pack_conv_bf16x3(t[DT_BT_CONV1_W], k.w1b, k.cout, k.cin, 3, k.cin_p, k.cin_w, k.n_p, k.split_c, k.split_cp, s);
-    if (!st) st = launch_pack_conv_bf16x3(t[DT_BT_CONV2_W], k.w2b, k.cout, k.cout, 3, k.cout_p, k.cout_w, k.n_p, k.cout, k.cout_p, s);
-    if (!st && k.has_res && j > 0)
-      st = launch_pack_conv_bf16x3(t[DT_BT_RES_W], k.wrb, k.cout, k.cin, 1, k.cin_p, k.cin_w, k.n_p, k.split_c, k.split_cp, s);
-    if (!st && j == 0) st = launch_pack_res3(t[DT_BT_RES_W], t[DT_BT_RES_B], k.w3, k.cout, C, k.n_p, s);
-    if (!st && j == 0 && u->share_enc1) st = launch_pack_tap_major(t[DT_BT_CONV2_W], S + o_w2t, k.cout, k.cout, k.cout_p, s);
-    if (!st) st = launch_fold_bn(t[DT_BT_CONV1_B], t[DT_BT_BN1_G], t[DT_BT_BN1_B], t[DT_BT_BN1_MEAN], t[DT_BT_BN1_VAR],
-                                 k.s1, k.h1, k.cout, k.n_p, s);
-    if (!st) st = launch_fold_bn(t[DT_BT_CONV2_B], t[DT_BT_BN2_G], t[DT_BT_BN2_B], t[DT_BT_BN2_MEAN], t[DT_BT_BN2_VAR],
-                                 k.s2, k.h2, k.cout, k.n_p, s);
-    if (!st && k.has_res && j > 0)
-      st = launch_fold_bn(t[DT_BT_RES_B], nullptr, nullptr, nullptr, nullptr, k.sr, k.hr, k.cout, k.n_p, s);
+    // a slot's conv bias and eval-BatchNorm tensors (the skip is a plain conv)
+    const float *const bn[3][5] = {{t[DT_BT_RES_B], nullptr, nullptr, nullptr, nullptr},
+                                   {t[DT_BT_CONV1_B], t[DT_BT_BN1_G], t[DT_BT_BN1_B], t[DT_BT_BN1_MEAN], t[DT_BT_BN1_VAR]},
+                                   {t[DT_BT_CONV2_B], t[DT_BT_BN2_G], t[DT_BT_BN2_B], t[DT_BT_BN2_MEAN], t[DT_BT_BN2_VAR]}};
+    for (int slot = 0; slot < 3 && st == DT_OK; ++slot) {
+      ConvW &c = k.c[slot];
+      const bool conv = has_launch(u, j, slot);
+      if (conv || (j == 0 && slot == 1)) {
+        c.w = S + o_c[j][slot].w;
+        c.scale = S + o_c[j][slot].ss; c.shift = c.scale + k.n_p;
+        st = launch_fold_bn(bn[slot][0], bn[slot][1], bn[slot][2], bn[slot][3], bn[slot][4], c.scale, c.shift, k.cout, k.n_p, s);
+      }
+      if (!conv) continue;
+      c.wb = S + o_c[j][slot].wb;
+      if (!st) st = launch_pack_conv(t[kSlotWeight[slot]], c.w, k.cout, c.cin, c.ksize, c.cin_p, k.n_p, c.split_c, c.split_cp, s);
+      if (!st) st = launch_pack_conv_bf16x3(t[kSlotWeight[slot]], c.wb, k.cout, c.cin, c.ksize, c.cin_p, c.cin_w, k.n_p, c.split_c, c.split_cp, s);
+    }
+    if (j == 0) {   // enc1's exceptions: conv1's own pack; the image skip's weights; conv2 tap-major for the class-bias columns
+      k.w3 = S + o_w3;
+      if (!st) st = launch_pack_first_conv(t[DT_BT_CONV1_W], k.c[1].w, k.cout, C, k.cout_p, s);
+      if (!st) st = launch_pack_res3(t[DT_BT_RES_W], t[DT_BT_RES_B], k.w3, k.cout, C, k.n_p, s);
+      if (!st && u->share_enc1) st = launch_pack_tap_major(t[DT_BT_CONV2_W], S + o_w2t, k.cout, k.cout, k.cout_p, s);
+    }
     if (!st) st = launch_pack_linear_rows(t[DT_BT_TIME_W], t[DT_BT_TIME_B], S + o_wt + (size_t)k.tb_off * D,
                                           S + o_bt + k.tb_off, k.cout, D, k.cout_p, s);
   }

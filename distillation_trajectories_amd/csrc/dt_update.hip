@@ -106,7 +106,7 @@ extern "C" int dt_cfg_update(int rule, const float *x, const float *eu, const fl
   if (B <= 0 || E <= 0 || E % 4) return DT_E_SHAPE;
   UpdateArgs a{x, eu, ec, z, z_row, w, out, {coef[0], coef[1], coef[2]}, w_scalar, 0, has_noise, B, E / 4, 0, 0, 0, 0};
   const size_t total = (size_t)B * (E / 4);
-  const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+  const int blocks = grid_blocks(total, 2048);
   // algorithmic bytes: read x + read z + write x' = 3*E*4 per sample-step (+ eps reads)
   ProfileScope prof(KC_UPDATE, 0.0, 4.0 * B * E * (2.0 + (has_noise ? 1.0 : 0.0) + (ec ? 2.0 : 1.0)), s);
   switch (rule) {
@@ -133,7 +133,7 @@ int launch_cfg_update_lowres(int rule, const float *x, const float *lowres_u, co
   UpdateArgs a{x, lowres_u, lowres_c, z, z_row, w, out, {coef[0], coef[1], coef[2]}, w_scalar, z_shift, has_noise, B, E / 4,
                H / 2, W / 2, H * W, b_single};
   const size_t total = (size_t)B * (E / 4);
-  const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+  const int blocks = grid_blocks(total, 2048);
   ProfileScope prof(KC_UPDATE, 0.0, 4.0 * B * E * (2.0 + (has_noise ? 1.0 : 0.0)) + 4.0 * B * H * W * (lowres_c ? 2.0 : 1.0), s);
   switch (rule) {
     case DT_RULE_ENGINE: cfg_update_kernel<DT_RULE_ENGINE, true><<<blocks, 256, 0, s>>>(a); break;
@@ -170,7 +170,7 @@ extern "C" int dt_q_sample(const float *x0, const float *z, const float *coef, i
   if (n_groups <= 0 || B <= 0 || E <= 0 || E % 4) return DT_E_SHAPE;
   if (((uintptr_t)x0 | (uintptr_t)z | (uintptr_t)out) & 15 || (uintptr_t)coef & 7) return DT_E_ARG;   // float4 / float2 accesses
   const size_t be4 = (size_t)B * (E / 4), total = (size_t)n_groups * be4;
-  const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+  const int blocks = grid_blocks(total, 2048);
   // algorithmic bytes: read z + write out per group, x0 once
   ProfileScope prof(KC_UPDATE, 3.0 * 4 * total, 4.0 * 4 * be4 * (2.0 * n_groups + 1.0), s);
   q_sample_kernel<<<blocks, 256, 0, s>>>(reinterpret_cast<const float4 *>(x0), reinterpret_cast<const float4 *>(z),

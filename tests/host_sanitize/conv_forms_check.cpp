@@ -4,6 +4,9 @@
 // here, in namespace `before`, as they were written (strip_kc, strip_lds_bytes, strip_lds_limit, kind_has_tile, the width
 // tests of conv_admissible, rows1 / rows2 / need of launch_conv_strip, epilogue_stage_floats): they are the expected
 // values and must never be rewritten in terms of the header.  sizeof(__bf16) is spelled sizeof(bf16_t).
+// The same for conv_real_channel, the padded-channel map of the weight packs: pack_conv_kernel, pack_conv_bf16x3_kernel and
+// pack_fused_conv_kernel each spelled it out (before::channel_fp32 / channel_bf16x3 / channel_fused, verbatim); for every
+// cin in 1..130 and every concat split of it the map over a pack's padded channels hits each real channel exactly once.
 #include <stdint.h>
 #include <stdio.h>
 
@@ -51,6 +54,28 @@ Stages stages(int kind, int bm, int bn) {
 
 // dt_conv_epilogue.h, the two GEMM kernels' stage (WM = 2)
 constexpr int epilogue_stage_floats(int BN, int WM = 2) { return WM * 32 * (BN + 4); }
+
+// pack_conv_kernel (dt_conv.hip), cp in [0, cin_p)
+int channel_fp32(int cp, int cin, int split_c, int split_cp) {
+  int c = -1;
+  if (cp < split_cp) { if (cp < split_c) c = cp; }
+  else { const int cc = split_c + (cp - split_cp); if (cc < cin) c = cc; }
+  return c;
+}
+// pack_conv_bf16x3_kernel (dt_conv_bf16.hip), cp in [0, cin_w)
+int channel_bf16x3(int cp, int cin, int cin_p, int split_c, int split_cp) {
+  int c = -1;
+  if (cp < split_cp) { if (cp < split_c) c = cp; }
+  else if (cp < cin_p) { const int cc = split_c + (cp - split_cp); if (cc < cin) c = cc; }
+  return c;
+}
+// pack_fused_conv_kernel (dt_fused.hip), cp in [0, kc * 16) = [0, cin_p)
+int channel_fused(int cp, int cin, int split_c, int split_cp) {
+  int ci;
+  if (cp < split_cp) ci = cp < split_c ? cp : -1;
+  else ci = cp - split_cp + split_c < cin ? cp - split_cp + split_c : -1;
+  return ci;
+}
 
 }  // namespace before
 
@@ -123,6 +148,31 @@ int main() {
   }
   for (int W = 1; W <= 64; ++W)
     EXPECT_EQ(find_conv_form(KIND_STRIP, 64, 64)->reaches(W), before::strip_reaches(W), "strip_reaches(%d)", W);
+  // ---- the padded-channel map: a plain input (split_c == cin) and every concat split of cin channels, padded as
+  // dt_unet_create pads them (each tensor to 16 channels, the split-bf16 pack to 64 per tap)
+  for (int cin = 1; cin <= 130; ++cin)
+    for (int split_c = 1; split_c <= cin; ++split_c) {
+      const int pad16 = 16, pad64 = 64;
+      const int split_cp = (split_c + pad16 - 1) / pad16 * pad16;
+      const int cin_p = split_c == cin ? split_cp : split_cp + (cin - split_c + pad16 - 1) / pad16 * pad16;
+      const int cin_w = (cin_p + pad64 - 1) / pad64 * pad64;
+      int hits[130] = {0};
+      long outside = 0;
+      for (int cp = 0; cp < cin_w; ++cp) {
+        const int c = conv_real_channel(cp, cin, cin_p, split_c, split_cp);
+        if (c >= 0 && c < cin) ++hits[c];
+        else outside += c != -1;
+        EXPECT_EQ(c, before::channel_bf16x3(cp, cin, cin_p, split_c, split_cp), "bf16x3 pack, cin %d split %d cp %d", cin, split_c, cp);
+        if (cp < cin_p) {
+          EXPECT_EQ(c, before::channel_fp32(cp, cin, split_c, split_cp), "fp32 pack, cin %d split %d cp %d", cin, split_c, cp);
+          EXPECT_EQ(c, before::channel_fused(cp, cin, split_c, split_cp), "fused pack, cin %d split %d cp %d", cin, split_c, cp);
+        } else {
+          EXPECT_EQ(c, -1, "zero chunk, cin %d split %d cp %d", cin, split_c, cp);
+        }
+      }
+      EXPECT_EQ(outside, 0, "values other than a real channel or -1, cin %d split %d", cin, split_c);
+      for (int c = 0; c < cin; ++c) EXPECT_EQ(hits[c], 1, "real channel %d of cin %d split %d", c, cin, split_c);
+    }
   printf("%s: %ld checks, %ld mismatches\n", failures ? "conv forms FAILED" : "conv forms ok", checks, failures);
   return failures ? 1 : 0;
 }

@@ -2,7 +2,9 @@
 
 tests/host_sanitize/conv_forms_check.cpp is plain C++: it includes the header, holds the earlier hand-written expressions
 (chunks per step, dynamic LDS per picture width, LDS limit, staging reach, epilogue stage and second stage, which
-(kind, tile) exist) and compares them with the members of every form for W = 1..64.  Built here with the host compiler
+(kind, tile) exist) and compares them with the members of every form for W = 1..64.  It does the same for the
+padded-channel map of the weight packs (conv_real_channel) against the three packers' earlier expressions, for every cin in
+1..130 and every concat split: each real channel exactly once, -1 everywhere else.  Built here with the host compiler
 under AddressSanitizer and UndefinedBehaviorSanitizer, then run."""
 import os
 import shutil

@@ -3,7 +3,8 @@ device-only for gfx950 and reads the compiler's own resource remarks (nothing is
 conv_strip_bf16x6_kernel<BM, BN, KC, WK> with WK > 1 must report 0
 spilled VGPRs and 0 bytes of scratch: scratch traffic inside a K walk hides what the walk costs.
 The three conv code objects together hold exactly the 21 forms of csrc/dt_conv_forms.h.  No kernel of the fp64 dense
-stages (csrc/dt_pca.hip, csrc/dt_fid.hip) may spill either."""
+stages (csrc/dt_pca.hip, csrc/dt_fid.hip) may spill either.  The eight tile-GEMM kernels keep their occupancy and LDS, and
+none spills more than it did before they came to share csrc/dt_conv_walk.h."""
 import functools
 import importlib.util
 import os
@@ -82,3 +83,30 @@ def test_conv_code_objects_hold_exactly_the_21_forms():
     got = [n for src in ("dt_conv.hip", "dt_conv_bf16.hip", "dt_conv_strip.hip") for n in _resources(src)
            if re.match(r"conv_\w+_kernel<", n)]
     assert len(FORMS) == 21 and sorted(got) == sorted(FORMS), sorted(set(got) ^ FORMS)
+
+
+# (occupancy, LDS bytes, spilled VGPRs, scratch bytes per lane) of the tile-GEMM kernels before csrc/dt_conv_walk.h
+# (profiles/kernel_resources.txt at that commit): the first two are exact, the last two upper bounds
+GEMM_RESOURCES = {
+    "conv_gemm_kernel<128,128>": (4, 33792, 578, 632),
+    "conv_gemm_kernel<128,64>": (4, 24576, 121, 168),
+    "conv_gemm_kernel<64,128>": (4, 33792, 190, 460),
+    "conv_gemm_kernel<64,64>": (4, 17408, 33, 80),
+    "conv_gemm_bf16x6_kernel<128,128>": (3, 49152, 348, 472),
+    "conv_gemm_bf16x6_kernel<128,64>": (3, 36864, 0, 0),
+    "conv_gemm_bf16x6_kernel<64,128>": (3, 36864, 106, 276),
+    "conv_gemm_bf16x6_kernel<64,64>": (3, 24576, 0, 0),
+}
+
+
+@pytest.mark.skipif(not _have_hipcc(), reason="hipcc is not installed")
+def test_tile_gemm_kernels_keep_their_resources():
+    """the shared K walk must not cost the two tile-GEMM kernels occupancy, LDS or registers"""
+    res = {**_resources("dt_conv.hip"), **_resources("dt_conv_bf16.hip")}
+    bad = {}
+    for name, (occ, lds, spill, scratch) in sorted(GEMM_RESOURCES.items()):
+        r = res[name]
+        print(f"{name}: occupancy {r['occupancy']}, {r['lds_bytes']} B LDS, {r['vgpr_spill']} spilled, {r['scratch_bytes']} B scratch")
+        if r["occupancy"] != occ or r["lds_bytes"] != lds or r["vgpr_spill"] > spill or r["scratch_bytes"] > scratch:
+            bad[name] = (r["occupancy"], r["lds_bytes"], r["vgpr_spill"], r["scratch_bytes"])
+    assert not bad, f"(occupancy, LDS, spilled VGPRs, scratch bytes) against {GEMM_RESOURCES}: {bad}"
