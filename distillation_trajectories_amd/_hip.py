@@ -128,6 +128,21 @@ LPIPS_SIGNATURES = {
                                        c_void_p]),
 }
 
+# name -> (restype, argtypes) of every symbol include/dt_hip_tsne.h declares (the t-SNE of the dimensionality analysis)
+TSNE_SIGNATURES = {
+    "dt_tsne_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dt_tsne_affinities": (c_int, [c_void_p, c_int, c_longlong, c_longlong, c_void_p, c_int, c_longlong, c_longlong, c_int,
+                                   c_int, c_double, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dt_tsne_descend": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+}
+
+
+class TsneParams(ctypes.Structure):
+    """dt_tsne_params of include/dt_hip_tsne.h"""
+    _fields_ = [("early_exaggeration", c_double), ("learning_rate", c_double), ("momentum", c_double * 2),
+                ("min_gain", c_double), ("min_grad_norm", c_double), ("exaggeration_iters", c_int),
+                ("n_iter_check", c_int), ("n_iter_without_progress", c_int * 2)]
+
 
 def load(path=None):
     """Load (once) and return the library with argtypes set.  Raises HipLibraryError if absent."""
@@ -145,7 +160,7 @@ def load(path=None):
     except OSError as e:
         raise HipLibraryError(f"cannot load {path}: {e}. There is no CPU fallback.") from e
     for name, (res, args) in {**SIGNATURES, **NOISE_SIGNATURES, **INCEPTION_SIGNATURES, **PCA_SIGNATURES,
-                              **FID_SIGNATURES, **LPIPS_SIGNATURES}.items():
+                              **FID_SIGNATURES, **LPIPS_SIGNATURES, **TSNE_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

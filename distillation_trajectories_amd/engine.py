@@ -727,6 +727,170 @@ def device_pca_project(a, mean, components, b=None):
     return out
 
 
+# ---------------------------------------------------------------------- t-SNE (include/dt_hip_tsne.h)
+TSNE_MAX_N = 512
+
+
+def tsne_state_doubles(n):
+    """doubles of descent state per problem: y, update, gains [n, 2] each, then ctl (DT_TSNE_STATE_DOUBLES)"""
+    return 6 * n + 4
+
+
+def tsne_state_views(state, n):
+    """{y, update, gains [P, n, 2], ctl [P, 4] = (best_error, best_iter, iterations done, stop reason)}: views of a
+    ``device_tsne`` state tensor [P, 6 n + 4]"""
+    P = state.shape[0]
+    return {"y": state[:, :2 * n].view(P, n, 2), "update": state[:, 2 * n:4 * n].view(P, n, 2),
+            "gains": state[:, 4 * n:6 * n].view(P, n, 2), "ctl": state[:, 6 * n:]}
+
+
+def _real(x, name, low=None, strict=True):
+    if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not math.isfinite(x):
+        raise ValueError(f"{name}={x!r} must be a finite number")
+    if low is not None and (x <= low if strict else x < low):
+        raise ValueError(f"{name}={x!r} must be {'>' if strict else '>='} {low}")
+    return float(x)
+
+
+def _count(x, name, low=0):
+    if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or x < low:
+        raise ValueError(f"{name}={x!r} must be an int >= {low}")
+    return int(x)
+
+
+def _tsne_check(a, b, perplexity, init, max_iter, it_begin, state, affinities, early_exaggeration, learning_rate,
+                n_iter_without_progress, min_grad_norm, exaggeration_iters, momentum, min_gain, n_iter_check):
+    """every argument error of ``device_tsne`` as a ValueError, before any device work; returns the rows, the shape and a
+    filled _hip.TsneParams"""
+    a = _pca_rows(a, "a")
+    b = None if b is None else _pca_rows(b, "b")
+    n_a, P, E = a.shape
+    n_b = 0 if b is None else b.shape[0]
+    if b is not None and tuple(b.shape[1:]) != (P, E):
+        raise ValueError(f"b {tuple(b.shape)} does not match a {tuple(a.shape)}: every row needs the same length and the "
+                         "same number of problems")
+    n = n_a + n_b
+    if not 4 <= n <= TSNE_MAX_N or n_a < 1:
+        raise ValueError(f"t-SNE needs 4 <= n <= {TSNE_MAX_N} rows (a first), got n_a={n_a}, n_b={n_b}")
+    if not 1 <= P <= 65535 or E < 1:
+        raise ValueError(f"unsupported shape: P={P}, E={E}")
+    perplexity = _real(perplexity, "perplexity", 0.0)
+    if perplexity >= n:
+        raise ValueError(f"perplexity={perplexity} must be less than n={n}")
+    it_begin, max_iter = _count(it_begin, "it_begin"), _count(max_iter, "max_iter")
+    if max_iter < it_begin:
+        raise ValueError(f"max_iter={max_iter} is below it_begin={it_begin}")
+    if (init is None) == (state is None):
+        raise ValueError("give exactly one of init (a fresh run) and state (a resumed one)")
+    if init is not None:
+        if isinstance(init, np.ndarray):
+            init = torch.from_numpy(np.array(init))
+        if not isinstance(init, torch.Tensor) or tuple(init.shape) not in ((n, 2), (P, n, 2)):
+            raise ValueError(f"init must be an array or tensor [n, 2] or [P, n, 2] = [{P}, {n}, 2], got "
+                             f"{tuple(init.shape) if hasattr(init, 'shape') else type(init).__name__}")
+        if not init.dtype.is_floating_point:
+            raise ValueError(f"init must be floating point, got {init.dtype}")
+    else:
+        if (not isinstance(state, torch.Tensor) or state.dtype != torch.float64
+                or tuple(state.shape) != (P, tsne_state_doubles(n))):
+            raise ValueError(f"state must be a float64 tensor [{P}, {tsne_state_doubles(n)}]")
+    if affinities is not None and (not isinstance(affinities, torch.Tensor) or affinities.dtype != torch.float64
+                                   or tuple(affinities.shape) != (P, n, n)):
+        raise ValueError(f"affinities must be a float64 tensor [{P}, {n}, {n}]")
+    prm = _hip.TsneParams()
+    prm.early_exaggeration = _real(early_exaggeration, "early_exaggeration", 0.0)
+    if isinstance(learning_rate, str):
+        if learning_rate != "auto":
+            raise ValueError(f"learning_rate={learning_rate!r} must be 'auto' or a positive number")
+        prm.learning_rate = max(n / prm.early_exaggeration / 4.0, 50.0)
+    else:
+        prm.learning_rate = _real(learning_rate, "learning_rate", 0.0)
+    if not isinstance(momentum, (tuple, list)) or len(momentum) != 2:
+        raise ValueError(f"momentum={momentum!r} must be a pair")
+    prm.momentum[0], prm.momentum[1] = _real(momentum[0], "momentum[0]"), _real(momentum[1], "momentum[1]")
+    prm.min_gain = _real(min_gain, "min_gain", 0.0, strict=False)
+    if isinstance(min_grad_norm, bool) or not isinstance(min_grad_norm, (int, float, np.integer, np.floating)) \
+            or not min_grad_norm >= 0:
+        raise ValueError(f"min_grad_norm={min_grad_norm!r} must be a number >= 0")
+    prm.min_grad_norm = float(min_grad_norm)
+    prm.exaggeration_iters = _count(exaggeration_iters, "exaggeration_iters")
+    prm.n_iter_check = _count(n_iter_check, "n_iter_check", 1)
+    if isinstance(n_iter_without_progress, (tuple, list)):
+        if len(n_iter_without_progress) != 2:
+            raise ValueError(f"n_iter_without_progress={n_iter_without_progress!r} must be an int or a pair")
+        pair = n_iter_without_progress
+    else:
+        pair = (prm.exaggeration_iters, n_iter_without_progress)       # sklearn: the exaggerated stage allows its own length
+    prm.n_iter_without_progress[0] = _count(pair[0], "n_iter_without_progress[0]")
+    prm.n_iter_without_progress[1] = _count(pair[1], "n_iter_without_progress")
+    return a, b, perplexity, init, prm
+
+
+def device_tsne(a, b=None, perplexity=30.0, init=None, max_iter=1000, early_exaggeration=12.0, learning_rate="auto",
+                n_iter_without_progress=300, min_grad_norm=1e-7, exaggeration_iters=250, momentum=(0.5, 0.8),
+                min_gain=0.01, n_iter_check=50, it_begin=0, state=None, affinities=None, return_affinities=False):
+    """Exact t-SNE (sklearn ``TSNE(method="exact")``, 2 components) of every problem p of the step-major device tensors
+    a [n_a, P, E] and b [n_b, P, E] (rows a[:, p] then b[:, p]; a 2-D [n, E] tensor is one problem; 4 <= n <= 512), in
+    place when the rows are 16-byte aligned and E % 4 == 0: dt_tsne_affinities, then iterations [it_begin, max_iter) of
+    dt_tsne_descend in one launch.
+
+    A fresh run takes ``init`` ([n, 2] for every problem, or [P, n, 2]); a resumed one takes the ``state`` an earlier call
+    returned and its ``it_begin``; the state given is not changed.  ``affinities`` [P, n, n] fp64 from an earlier call
+    skips their computation.  ``n_iter_without_progress`` is sklearn's argument (the exaggerated stage then allows
+    ``exaggeration_iters``, as sklearn does) or a pair.  Returns device tensors {embedding [P, n, 2] fp32, kl_divergence
+    [P] fp64 (of the returned embedding), n_iter [P] int32 (iterations done), status [P] int32 (0 ok, 1 non-finite input:
+    embedding and KL are NaN), state [P, 6 n + 4] fp64 (``tsne_state_views``)} and, with ``return_affinities``,
+    affinities [P, n, n] fp64."""
+    a, b, perplexity, init, prm = _tsne_check(a, b, perplexity, init, max_iter, it_begin, state, affinities,
+                                              early_exaggeration, learning_rate, n_iter_without_progress, min_grad_norm,
+                                              exaggeration_iters, momentum, min_gain, n_iter_check)
+    _require_cuda(a, "a")
+    if b is not None:
+        _require_cuda(b, "b")
+    lib = _hip.load()
+    n_a, P, E = a.shape
+    n_b = 0 if b is None else b.shape[0]
+    n, E4 = n_a + n_b, E + (-E % 4)
+    dev = a.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        if affinities is None:
+            a = _pca_pad(a, E4)                              # squared distances are blind to zero columns
+            b = None if b is None else _pca_pad(b, E4)
+            ws_bytes = lib.dt_tsne_workspace_bytes(P, n, E4)
+            if ws_bytes == 0:
+                raise ValueError(f"dt_tsne_workspace_bytes rejects P={P}, n={n}, E={E4}")
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            p_mat = torch.empty(P, n, n, **f64)
+            status = torch.empty(P, dtype=torch.int32, device=dev)
+            bs = (0, 0) if b is None else (b.stride(1), b.stride(0))
+            check(lib.dt_tsne_affinities(ptr(a), n_a, a.stride(1), a.stride(0), ptr(b), n_b, bs[0], bs[1], P, E4,
+                                         perplexity, ptr(p_mat), ptr(status), ptr(ws), ws_bytes, stream_ptr()),
+                  "dt_tsne_affinities")
+        else:
+            p_mat = affinities.to(dev).contiguous()
+            status = torch.isnan(p_mat[:, 0, 1]).to(torch.int32)
+        if state is None:
+            y0 = init.to(dev, torch.float64)
+            y0 = y0.expand(P, n, 2) if y0.dim() == 2 else y0
+            state = torch.zeros(P, tsne_state_doubles(n), **f64)
+            views = tsne_state_views(state, n)
+            views["y"].copy_(y0)
+            views["gains"].fill_(1.0)
+            views["ctl"][:, 0] = sys.float_info.max
+        else:
+            state = state.to(dev).clone()
+        embedding = torch.empty(P, n, 2, dtype=torch.float32, device=dev)
+        kl = torch.empty(P, **f64)
+        check(lib.dt_tsne_descend(ptr(p_mat), P, n, ptr(state), it_begin, max_iter, ctypes.byref(prm), ptr(embedding),
+                                  ptr(kl), stream_ptr()), "dt_tsne_descend")
+        out = {"embedding": embedding, "kl_divergence": kl, "n_iter": state[:, 6 * n + 2].to(torch.int32),
+               "status": status, "state": state}
+    if return_affinities:
+        out["affinities"] = p_mat
+    return out
+
+
 # ---------------------------------------------------------------------- Fréchet distance (include/dt_hip_fid.h)
 FID_MAX_SIDE = 2048
 FID_MAX_ROWS = 32768
