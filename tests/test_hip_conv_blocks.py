@@ -15,8 +15,42 @@ float64 reference is computed once per case from that input:
 
 The cases cover the ragged M tiles of 41 images (4x4 / 2x2 / 1x1 levels), the 256 x 64 tiles and the epilogue modes of the
 half-size model, odd channel counts (38 / 51 channels), 32 x 32 pictures (2 x 2 bottleneck), a mixed batch (shared enc1 with
-single-pass images) and a one-pass forward (a pin keyed by the one-pass image split).  Every case runs every launch the
-rules admit (about 8800 in all, twice each: on one MI355X the module takes about 16 s).
+single-pass images) and a one-pass forward (a pin keyed by the one-pass image split); and five rectangular pictures whose
+level widths are no power of two (cases G .. K, see CASES), where no tile height is a multiple of the width: every strip
+tile starts and ends inside a picture row and takes the halo W + 1 (strip_halo), rows and columns are told apart, the
+bottleneck is a 1 x 3 or a 3 x 1 picture that walks nine taps, a width of 56 puts the K = 32 forms 256 x 64 and 128 x 128 at their
+LDS limit of 98 304 B (48 px: 95 232 B), and levels of 112 / 80 pixels fall back to the GEMM kinds.
+
+  case                        H x W    B   admissible  run   refused at launch (stripk 64 x 64 on rows > 31 px)
+  A_sf1.0_16px_B41           16 x 16  41      1472     1472  -
+  B_sf0.5_16px_B41           16 x 16  41      1253     1253  -
+  C_sf0.3_16px_B41           16 x 16  41       996      996  -
+  C_sf0.4_16px_B41           16 x 16  41       970      970  -
+  D_sf1.0_32px_B5            32 x 32   5      1606     1605  enc1.conv2 (32 px)
+  E_sf0.5_mixed_B9_single3   16 x 16   9+6    1253     1253  -
+  F_sf0.5_one_pass_B12       16 x 16  12      1253     1253  -
+  G_sf0.5_16x48_B5           16 x 48   5      1371     1370  enc1.conv2 (48 px)
+  H_sf0.5_48x16_B5           48 x 16   5      1371     1371  -
+  I_sf0.5_16x112_B2          16 x 112  2      1363     1354  enc2 and dec1 (56 px), 9 launches
+  J_sf0.3_32x48_B3           32 x 48   3      1138     1137  enc1.conv2 (48 px)
+  K_sf1.0_16x80_B3           16 x 80   3      1593     1580  enc2 and dec1 (40 px), 13 launches
+
+(min_launches is that count rounded down.)  On G, H and J the strip kinds 3 / 4 / 5 ran on every 3x3 slot with every
+tile the channel count admits (kind 5's 64 x 64 tile up to 31 px); on I's 56 px levels kind 4 ran 256 x 64, 128 x 128, 128 x 64,
+64 x 128 and 64 x 64 -- nothing is refused at 56, 48 or 40 px but stripk 64 x 64.
+
+What a pinned conv2 launch writes besides its block output:
+
+  * head fusion on, for every dec1.conv2 pin: eps agrees with the head-off eps of the same pin to REL_L2 per row and is
+    bit-identical under both poisons; dec1's output is left unwritten exactly where the rule fuses the head (one N tile, no
+    split).  For every enc1.conv2 pin: enc2's output is bit-identical to the head-off run of the same pin, and enc1's own
+    output is left unwritten exactly where its epilogue pools (skip_out);
+  * test_pinned_conv2_launches_write_the_max_pool: the 2x2 max pool behind enc1 .. enc4, written by conv2's staged epilogue,
+    by the slab sum of a split launch or by maxpool_kernel, read back exactly through a transparent next block.
+
+Every case runs every launch the rules admit (about 15600 in all, twice each, the 880 pool pins and the 920 head-fusion
+reruns aside): on one MI355X the module takes about 26 s (16 s before cases G .. K and the pool test; each new case 1.6 to
+2.8 s, each pool shape 0.3 to 0.4 s).
 """
 import math
 import random
@@ -37,13 +71,15 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 # Elementwise bound TAU * S with TAU = C_TAU * 2^-24.  Measured on an MI355X over every launch of every case: max err / S
-# = 0.50 * 2^-24 (fp32 0.42, split-bf16 0.50, strip 0.47, strip32 0.44, stripk 0.40); C_TAU keeps a 4x margin
+# = 0.50 * 2^-24 (fp32 0.42, split-bf16 0.50, strip 0.47, strip32 0.44, stripk 0.40); C_TAU keeps a 4x margin.  The
+# rectangular cases G .. K alone: 0.42 (fp32 0.37, split-bf16 0.41, strip 0.42, strip32 0.42, stripk 0.31) -- an output
+# element's fma chain is as long on any picture shape, out-of-picture taps add nothing
 C_TAU = 2
 TAU = C_TAU * 2.0 ** -24
-REL_L2 = 1e-6                    # per-image relative L2 error of a block output against float64 (measured max 5.2e-7)
-# per-image RMS of err / S, in units of 2^-24: measured max 0.096 (fp32, split-bf16 GEMM kinds), 0.045 (strip kinds).  Far
-# below the elementwise bound, it sees errors the size of fp32 rounding spread over a whole image, e.g. one of the six
-# plane products of a strip kind dropped (0.29)
+REL_L2 = 1e-6                    # per-image relative L2 error of a block output against float64 (measured max 5.2e-7; G .. K 5.0e-7)
+# per-image RMS of err / S, in units of 2^-24: measured max 0.096 (fp32, split-bf16 GEMM kinds), 0.045 (strip kinds); on
+# G .. K 0.033 (fp32), 0.036 (split-bf16 and the strip kinds).  Far below the elementwise bound, it sees errors the size of
+# fp32 rounding spread over a whole image, e.g. one of the six plane products of a strip kind dropped (0.29)
 RMS_C = 0.2
 POISONS = (float("nan"), 1e30)   # fmaxf-style ReLUs turn a NaN read into 0: a large finite value is needed too
 KDIV = (1, 2, 4, 8, 16, 8, 4, 2)
@@ -56,6 +92,7 @@ class Case(NamedTuple):
     name: str
     sf: float
     H: int
+    W: int
     B: int
     n_pass: int
     single: int      # single-pass images of a mixed batch (dt_unet_forward_mixed)
@@ -65,13 +102,19 @@ class Case(NamedTuple):
 
 
 CASES = (
-    Case("A_sf1.0_16px_B41", 1.0, 16, 41, 2, 0, 41, 1400, 1),
-    Case("B_sf0.5_16px_B41", 0.5, 16, 41, 2, 0, 1, 1200, 2),
-    Case("C_sf0.3_16px_B41", 0.3, 16, 41, 2, 0, 1, 950, 3),
-    Case("C_sf0.4_16px_B41", 0.4, 16, 41, 2, 0, 1, 920, 4),
-    Case("D_sf1.0_32px_B5", 1.0, 32, 5, 2, 0, 1, 1500, 5),
-    Case("E_sf0.5_mixed_B9_single3", 0.5, 16, 9, 2, 3, 1, 1200, 6),
-    Case("F_sf0.5_one_pass_B12", 0.5, 16, 12, 1, 0, 1, 1200, 7),
+    Case("A_sf1.0_16px_B41", 1.0, 16, 16, 41, 2, 0, 41, 1400, 1),
+    Case("B_sf0.5_16px_B41", 0.5, 16, 16, 41, 2, 0, 1, 1200, 2),
+    Case("C_sf0.3_16px_B41", 0.3, 16, 16, 41, 2, 0, 1, 950, 3),
+    Case("C_sf0.4_16px_B41", 0.4, 16, 16, 41, 2, 0, 1, 920, 4),
+    Case("D_sf1.0_32px_B5", 1.0, 32, 32, 5, 2, 0, 1, 1500, 5),
+    Case("E_sf0.5_mixed_B9_single3", 0.5, 16, 16, 9, 2, 3, 1, 1200, 6),
+    Case("F_sf0.5_one_pass_B12", 0.5, 16, 16, 12, 1, 0, 1, 1200, 7),
+    # rectangular pictures: no tile height is a multiple of the level width, so every strip tile takes the halo W + 1
+    Case("G_sf0.5_16x48_B5", 0.5, 16, 48, 5, 2, 0, 1, 1350, 8),      # rows of 48 .. 3 px; the bottleneck is 1 x 3 (nine taps)
+    Case("H_sf0.5_48x16_B5", 0.5, 48, 16, 5, 2, 0, 1, 1350, 9),      # heights 48 .. 3 on widths 16 .. 1; the bottleneck is 3 x 1
+    Case("I_sf0.5_16x112_B2", 0.5, 16, 112, 2, 2, 0, 1, 1350, 10),   # 112 px: GEMM kinds only; 56 px: strip forms at their LDS limit
+    Case("J_sf0.3_32x48_B3", 0.3, 32, 48, 3, 2, 0, 1, 1100, 11),     # 38 / 76 channels with the halo W + 1
+    Case("K_sf1.0_16x80_B3", 1.0, 16, 80, 3, 2, 0, 1, 1550, 12),     # bn = 128 forms; 80 px GEMM only, 40 px without stripk 64 x 64
 )
 
 
@@ -173,12 +216,12 @@ class Runner:
         self.imgs = row_images(c)
         self.rows = len(self.imgs)
         g = torch.Generator().manual_seed(1000 + c.seed)
-        self.x = torch.randn(c.B, 3, c.H, c.H, generator=g)
+        self.x = torch.randn(c.B, 3, c.H, c.W, generator=g)
         self.x_dev = self.x.to(DEV)
         self.conds = row_conditions(c)
         self.tb = self.h.time_bias([t for t, _ in self.conds], [m for _, m in self.conds])
-        self.ws = self.h.workspace(self.rows, c.H, c.H)
-        self.eps = torch.empty(self.rows, 3, c.H, c.H, dtype=torch.float32, device=DEV)
+        self.ws = self.h.workspace(self.rows, c.H, c.W)
+        self.eps = torch.empty(self.rows, 3, c.H, c.W, dtype=torch.float32, device=DEV)
         self.couts = [sd32[f"{n}.conv2.weight"].shape[0] for n in engine.BLOCK_NAMES]
 
     # -- library calls
@@ -187,9 +230,9 @@ class Runner:
         c, h = self.c, self.h
         with torch.cuda.device(DEV):
             if c.single:
-                return h.lib.dt_unet_forward_mixed(h.h, ptr(self.x_dev), c.B, c.single, c.H, c.H, ptr(self.tb), c.tb_div,
+                return h.lib.dt_unet_forward_mixed(h.h, ptr(self.x_dev), c.B, c.single, c.H, c.W, ptr(self.tb), c.tb_div,
                                                    ptr(self.eps), ptr(self.ws), c_size_t(self.ws.numel()), stream_ptr())
-            return h.lib.dt_unet_forward(h.h, ptr(self.x_dev), c.B, c.n_pass, c.H, c.H, ptr(self.tb), c.tb_div, ptr(self.eps),
+            return h.lib.dt_unet_forward(h.h, ptr(self.x_dev), c.B, c.n_pass, c.H, c.W, ptr(self.tb), c.tb_div, ptr(self.eps),
                                          ptr(self.ws), c_size_t(self.ws.numel()), stream_ptr())
 
     def poisoned_forward(self, value):
@@ -198,13 +241,13 @@ class Runner:
         return self.forward()
 
     def act(self, j):
-        return self.h.debug_activation(self.rows, self.c.H, self.c.H, j)
+        return self.h.debug_activation(self.rows, self.c.H, self.c.W, j)
 
     def report(self, j, slot, split=None):
         """dt_unet_conv_choice's report for the case's own shape, or for another (images, single-pass images) of its rows"""
         v = [c_int() for _ in range(5)]
         imgs, single = split or (self.c.B, self.c.single)
-        check(self.h.lib.dt_unet_conv_choice(self.h.h, self.rows, self.c.H, self.c.H, imgs, single, j, slot, *map(byref, v)), "dt_unet_conv_choice")
+        check(self.h.lib.dt_unet_conv_choice(self.h.h, self.rows, self.c.H, self.c.W, imgs, single, j, slot, *map(byref, v)), "dt_unet_conv_choice")
         return tuple(x.value for x in v)
 
     def pin(self, j, slot, bm, bn, splits, kind, fuse):
@@ -213,18 +256,18 @@ class Runner:
         h.set_precision(_hip.PREC_AUTO)
         try:
             if slot == 0:
-                h.set_conv_choice(self.rows, c.H, c.H, j, 2, *SKIP_CONV2, images=c.B, single=c.single)
-            h.set_conv_choice(self.rows, c.H, c.H, j, slot, bm, bn, splits, kind, fuse, images=c.B, single=c.single)
+                h.set_conv_choice(self.rows, c.H, c.W, j, 2, *SKIP_CONV2, images=c.B, single=c.single)
+            h.set_conv_choice(self.rows, c.H, c.W, j, slot, bm, bn, splits, kind, fuse, images=c.B, single=c.single)
         except HipLibraryError:
             return False
         return True
 
     # -- the launch vocabulary
-    def admissible(self):
+    def admissible(self, blocks=range(8), slots=range(3)):
         """{(j, slot, resolved report [bm, bn, splits, kind + 8 fuse]): request} over the whole vocabulary"""
         found = {}
-        for j in range(8):
-            for slot in range(3):
+        for j in blocks:
+            for slot in slots:
                 for bm in AXES["bm"]:
                     for bn in AXES["bn"]:
                         for sp in AXES["splits"]:
@@ -242,10 +285,17 @@ class Runner:
         return found
 
 
+def level(c, j):
+    """(height, width) of block j's pictures"""
+    return c.H // KDIV[j], c.W // KDIV[j]
+
+
 def expected_kinds(c, j, slot):
-    """launch kinds the rules admit for a slot: the strip kinds need a full 3x3 walk (not a 1x1 conv or a 1x1 picture)"""
-    side = c.H // KDIV[j]
-    return {0, 1} if slot == 0 or side == 1 else {0, 1, 3, 4, 5}
+    """launch kinds the rules admit for a slot (resolve_conv_choice, conv_layer): the strip kinds need a full 3x3 walk -- not
+    a 1x1 conv, and not a 1x1 picture, whose convolutions keep the centre tap only; a 1 x 3 or 3 x 1 picture walks all nine
+    -- over picture rows of at most 63 pixels"""
+    h, w = level(c, j)
+    return {0, 1} if slot == 0 or (h == 1 and w == 1) or w > 63 else {0, 1, 3, 4, 5}
 
 
 def check_block(got, ref, S, cout):
@@ -265,7 +315,20 @@ def bits(t):
     return t.contiguous().view(torch.int32)
 
 
-def run_case(c, models, stats):
+def dec1_head_fuses(run, rep):
+    """resolve_forward: dec1.conv2 evaluates the 1x1 head where its workgroups hold whole rows -- one N tile, no split"""
+    return rep[2] == 1 and rep[1] == -(-run.couts[7] // 64) * 64
+
+
+def enc1_pools_in_epilogue(c):
+    """resolve_forward's pool rule for enc1.conv2 (never split): its staged epilogue pools where W is a power of two <= 16;
+    with head fusion on, shared enc1 then stores the pool alone (skip_out)"""
+    w = c.W
+    return w <= 16 and w & (w - 1) == 0
+
+
+def run_case(c, models, stats, log=None):
+    """log: a list that receives (launch, [its failures]) of every launch run (tools)"""
     sd32 = {k: v.float() for k, v in models(c.sf).state_dict().items() if v.dtype.is_floating_point}
     sd64 = {k: v.double() for k, v in sd32.items()}
     run = Runner(c, sd32)
@@ -275,19 +338,19 @@ def run_case(c, models, stats):
         # the pin of a one-pass shape made before its first forward is the one the forward runs (the library would otherwise
         # key it by the two-pass split images = rows / 2)
         ref_j, ref_slot = 2, 1
-        h.set_conv_choice(rows, c.H, c.H, ref_j, ref_slot, 64, 64, 1, _hip.KIND_FP32, 0, images=c.B)
+        h.set_conv_choice(rows, c.H, c.W, ref_j, ref_slot, 64, 64, 1, _hip.KIND_FP32, 0, images=c.B)
         h.forward(run.x_dev, run.tb, c.n_pass, c.tb_div)
         rep = run.report(ref_j, ref_slot)
         assert rep == (64, 64, 1, _hip.KIND_FP32, 1), f"pin before the first one-pass forward was dropped: report {rep}"
         assert set(h.plan_ids().values()) == {"pinned"}, h.plan_ids()
         # the pin belongs to that split alone: another split of the same rows (the two-pass one) settles a plan of its own
-        other = h.ensure_plan(rows, c.H, c.H, rows // 2, 0)
+        other = h.ensure_plan(rows, c.H, c.W, rows // 2, 0)
         assert other != "pinned" and run.report(ref_j, ref_slot, (rows // 2, 0))[4] == 0, (other, h.plan_ids())
-        assert h.ensure_plan(rows, c.H, c.H, c.B, c.single) == "pinned" and run.report(ref_j, ref_slot) == rep, h.plan_ids()
+        assert h.ensure_plan(rows, c.H, c.W, c.B, c.single) == "pinned" and run.report(ref_j, ref_slot) == rep, h.plan_ids()
         h.set_precision(_hip.PREC_AUTO)            # drops the pins: the next forward settles its own plan
         h.forward(run.x_dev, run.tb, c.n_pass, c.tb_div)
         assert "pinned" not in h.plan_ids().values() and run.report(ref_j, ref_slot)[4] == 0, h.plan_ids()
-    h.ensure_plan(rows, c.H, c.H, c.B, c.single, tune=False)
+    h.ensure_plan(rows, c.H, c.W, c.B, c.single, tune=False)
 
     # the heuristic plan's block outputs: the inputs of the references, and what every pinned forward must leave upstream
     h.set_precision(_hip.PREC_AUTO)
@@ -312,7 +375,9 @@ def run_case(c, models, stats):
     assert len(found) >= c.min_launches, f"{c.name}: the rules admit only {len(found)} distinct launches"
 
     failures, ran, refused, seen = [], 0, [], defaultdict(set)
+    strip_ran, head_runs = defaultdict(set), [0, 0, 0, 0]   # [dec1.conv2 pins, with the head fused, enc1.conv2 pins, under skip_out]
     for key in [None] + sorted(found):
+        n_before = len(failures)
         if key is None:                       # the heuristic plan itself
             j, slot, what = None, None, "heuristic plan"
             h.set_precision(_hip.PREC_AUTO)
@@ -332,6 +397,8 @@ def run_case(c, models, stats):
             check(status, f"dt_unet_forward ({what})")
             blocks = range(8) if j is None else [j]
             outs.append(([run.act(b).clone() for b in blocks], run.eps.clone()))
+            if j == 0:
+                next_off = run.act(1).clone()
             if j is not None:
                 flags += [(bits(run.act(u)) != bits(base[0][0][u])).any() for u in range(j)]
         if status < 0:
@@ -363,10 +430,38 @@ def run_case(c, models, stats):
                 st = stats[kind]
                 st[0], st[1], st[2], st[3] = max(st[0], ratio * 2 ** 24), max(st[1], rel), max(st[2], rms * 2 ** 24), st[3] + 1
                 seen[(j, slot)].add(kind)
+                if kind >= 3:
+                    strip_ran[(level(c, j)[1], kind)].add(key[2:4])
         if not torch.equal(bits(outs[0][1]), bits(outs[1][1])) or not torch.isfinite(outs[0][1]).all():
             failures.append(f"{what}: eps differs between poisons or is not finite")
         if flags and torch.stack(flags).any().item():
             failures.append(f"{what}: a block upstream of the pinned one changed")
+        if slot == 2 and j in (0, 7):
+            # the same pin with head fusion on (the default).  dec1.conv2: its epilogue evaluates the 1x1 head where the rule
+            # says so and dec1's output is then not stored; eps against the head-off eps of this pin.  enc1.conv2: it stores
+            # the pool alone where its epilogue pools (skip_out); enc2's output is bit-identical to the head-off run of this pin
+            h.set_head_fusion(True)
+            on = []
+            for value in POISONS:
+                check(run.poisoned_forward(value), f"dt_unet_forward ({what}, head fusion on)")
+                on.append((run.act(1).clone(), run.eps.clone(), torch.isnan(run.act(j)).all().item()))
+            h.set_head_fusion(False)
+            if not torch.equal(bits(on[0][1]), bits(on[1][1])) or not torch.isfinite(on[0][1]).all():
+                failures.append(f"{what}: head fusion on, eps differs between poisons or is not finite")
+            unstored = dec1_head_fuses(run, key[2:]) if j == 7 else enc1_pools_in_epilogue(c)
+            if on[0][2] != unstored:         # (first poison: NaN)
+                failures.append(f"{what}: head fusion on, the block output is {'not ' if on[0][2] else ''}stored")
+            head_runs[0 if j == 7 else 2] += 1
+            head_runs[1 if j == 7 else 3] += unstored
+            if j == 7:
+                e_on, e_off = on[0][1].double(), outs[0][1].double()
+                rel_eps = ((e_on - e_off).flatten(1).norm(dim=1) / e_off.flatten(1).norm(dim=1)).max().item()
+                if not rel_eps <= REL_L2:
+                    failures.append(f"{what}: eps with head fusion on differs by {rel_eps:.3e} (relative L2, worst row)")
+            elif not torch.equal(bits(on[0][0]), bits(next_off)):
+                failures.append(f"{what}: head fusion on changes enc2's output")
+        if log is not None:
+            log.append((what, failures[n_before:]))
 
     # head fusion on (the default): the heuristic plan's stored block outputs are bit-identical to the head-off run, eps agrees
     h.set_head_fusion(True)
@@ -387,12 +482,16 @@ def run_case(c, models, stats):
     assert rel_eps <= REL_L2, f"{c.name}: eps with the fused head differs by {rel_eps:.3e} (relative L2, worst row)"
 
     print(f"\n{c.name}: {len(found)} admissible launches, {ran - 1} run, refused at launch: {refused}, head-fused eps "
-          f"{'bit-identical' if torch.equal(fused[0][1], base[0][1]) else f'rel L2 {rel_eps:.2e}'}")
+          f"{'bit-identical' if torch.equal(fused[0][1], base[0][1]) else f'rel L2 {rel_eps:.2e}'}; head fusion on under pins: "
+          f"{head_runs[0]} dec1.conv2 ({head_runs[1]} with the head in the epilogue), {head_runs[2]} enc1.conv2 ({head_runs[3]} "
+          f"storing the pool alone)")
+    print("  strip tiles run, by picture width: " + "; ".join(
+        f"{w} px {_hip.KIND_NAMES[k]} " + " ".join(f"{bm}x{bn}" for bm, bn in sorted(t)) for (w, k), t in sorted(strip_ran.items())))
     assert not failures, f"{c.name}: {len(failures)} failures:\n  " + "\n  ".join(failures[:40])
-    # the one choice the rules admit and the launcher refuses: stripk's 64 x 64 tile (one strip item per thread) on rows of
-    # more than 31 pixels
+    # the one choice the rules admit and the launcher refuses: stripk's 64 x 64 tile (one strip item per thread) on picture
+    # rows of more than 31 pixels
     for j, slot, bm, bn, _, kind in refused:
-        assert (kind & 7, bm, bn) == (5, 64, 64) and c.H // KDIV[j] > 31, f"{c.name}: launch {(j, slot, bm, bn, kind)} refused"
+        assert (kind & 7, bm, bn) == (5, 64, 64) and level(c, j)[1] > 31, f"{c.name}: launch {(j, slot, bm, bn, kind)} refused"
     for (j, slot), kinds in admitted.items():
         assert seen[(j, slot)] == kinds, f"{c.name}: {engine.BLOCK_NAMES[j]}.{SLOT_NAMES[slot]} ran kinds {sorted(seen[(j, slot)])} of {sorted(kinds)}"
 
@@ -400,6 +499,96 @@ def run_case(c, models, stats):
 @pytest.mark.parametrize("case", CASES, ids=[c.name for c in CASES])
 def test_conv_launches_block_by_block_vs_float64(case, models, cpu_threads, stats):
     run_case(case, models, stats)
+
+
+# ------------------------------------------------------------------ the 2x2 max pool a pinned conv2 launch leaves behind
+POOL_SHAPES = (
+    Case("P_sf0.5_16x16_B5", 0.5, 16, 16, 5, 2, 0, 1, 0, 21),    # 16 / 8 px: the tile epilogues pool; splits: the slab sum pools
+    Case("P_sf0.5_16x48_B3", 0.5, 16, 48, 3, 2, 0, 1, 0, 22),    # 48 .. 6 px: maxpool_kernel, and the slab sum under splits
+    Case("P_sf0.3_32x32_B3", 0.3, 32, 32, 3, 2, 0, 1, 0, 23),    # 38 / 76 channels; 32 px: maxpool_kernel; then 16 .. 4 px
+)
+POOL_PATHS = ("tile epilogue", "slab sum", "maxpool_kernel")
+
+
+def transparent(sd32, j):
+    """the weights with block j made transparent: norm2's weight and bias zero, so relu(bn2(conv2)) is exactly 0 and the block
+    output is its skip path alone -- the input itself (identity skips), or, where the block has a 1x1 residual_conv, output
+    channel n = input channel n % cin through a 0 / 1 selection with zero bias"""
+    sd, name = dict(sd32), engine.BLOCK_NAMES[j]
+    for key in (f"{name}.norm2.weight", f"{name}.norm2.bias"):
+        sd[key] = torch.zeros_like(sd[key])
+    if f"{name}.residual_conv.weight" in sd:
+        w = torch.zeros_like(sd[f"{name}.residual_conv.weight"])
+        cout, cin = w.shape[:2]
+        w[torch.arange(cout), torch.arange(cout) % cin, 0, 0] = 1.0
+        sd[f"{name}.residual_conv.weight"] = w
+        sd[f"{name}.residual_conv.bias"] = torch.zeros_like(sd[f"{name}.residual_conv.bias"])
+    return sd
+
+
+def pool_path(c, j, splits):
+    """which launch writes enc(j+1)'s pooled output (resolve_forward's pool_fused, heights and widths being even): the slab
+    sum of a split conv2, else conv2's staged epilogue where W is a power of two <= 16, else maxpool_kernel"""
+    w = level(c, j)[1]
+    return POOL_PATHS[1] if splits > 1 else POOL_PATHS[0] if w <= 16 and w & (w - 1) == 0 else POOL_PATHS[2]
+
+
+def pool_reference(a):
+    """2x2 max pool of an NHWC block output, by torch on the device (exact: a maximum rounds nothing)"""
+    return F.max_pool2d(a.permute(0, 3, 1, 2), 2).permute(0, 2, 3, 1)
+
+
+@pytest.mark.parametrize("case", POOL_SHAPES, ids=[c.name for c in POOL_SHAPES])
+def test_pinned_conv2_launches_write_the_max_pool(case, models):
+    """For j = enc1 .. enc4 every admissible conv2 pin (each tile, kind, split count, with and without the folded skip), with
+    block j + 1 transparent: block j + 1's output then IS the pooled tensor the pinned launch (or maxpool_kernel behind it)
+    wrote, and must equal max_pool2d of block j's output of the same run, number for number, under both poisons.  (The 0 / 1
+    selection of transparent enc2 is exact in the split-bf16 walk too: the three bf16 planes of x sum to x, the other
+    products are 0.)  Which of the three pool paths a pin takes follows from the rule and the reported split count; every path
+    the shape's levels allow must have run."""
+    c = case
+    sd32 = {k: v.float() for k, v in models(c.sf).state_dict().items() if v.dtype.is_floating_point}
+    found, failures, pins, refused, paths = None, [], 0, [], defaultdict(int)
+    for j in range(4):
+        run = Runner(c, transparent(sd32, j + 1))
+        run.h.ensure_plan(run.rows, c.H, c.W, c.B, c.single, tune=False)
+        if found is None:
+            found = run.admissible(range(4), [2])       # (the rules see shapes, not weights: one enumeration serves all four)
+        cout, cnext = run.couts[j], run.couts[j + 1]
+        sel = torch.arange(cnext, device=DEV) % cout
+        for key in sorted(k for k in found if k[0] == j):
+            what = f"{engine.BLOCK_NAMES[j]}.conv2 {_hip.KIND_NAMES[key[5] & 7]} {key[2]}x{key[3]} s{key[4]}{' +skip' if key[5] & 8 else ''}"
+            assert run.pin(j, 2, *found[key]), what
+            assert run.report(j, 2)[:4] == key[2:], f"{what}: resolves differently on this handle"
+            path = pool_path(c, j, key[4])
+            got, why, status = [], [], 0
+            for value in POISONS:
+                status = run.poisoned_forward(value)
+                if status < 0:
+                    break
+                check(status, f"dt_unet_forward ({what})")
+                nxt = run.act(j + 1)
+                if not torch.equal(nxt[..., :cnext], pool_reference(run.act(j)[..., :cout])[..., sel]):
+                    why.append(f"poison {value}: block {j + 1}'s input is not the 2x2 max pool of block {j}'s output")
+                if (nxt[..., cnext:] != 0).any().item():
+                    why.append(f"poison {value}: nonzero padding channels")
+                got.append(nxt.clone())
+            if status < 0:
+                refused.append(key)
+                continue
+            if not torch.equal(bits(got[0]), bits(got[1])):
+                why.append("the pooled tensor differs between the poisons")
+            pins += 1
+            paths[path] += 1
+            if why:
+                failures.append(f"{what} (pool by {path}): " + "; ".join(why))
+    print(f"\n{c.name}: {pins} conv2 pins, pool written by: " + ", ".join(f"{p} {paths[p]}" for p in POOL_PATHS) + f"; refused at launch: {refused}")
+    assert not failures, f"{c.name}: {len(failures)} of {pins} pins fail:\n  " + "\n  ".join(failures[:40])
+    for j, slot, bm, bn, _, kind in refused:
+        assert (kind & 7, bm, bn) == (5, 64, 64) and level(c, j)[1] > 31, f"{c.name}: launch {(j, slot, bm, bn, kind)} refused"
+    # enc2 .. enc4 are splittable at these sizes (fewer than 32768 GEMM rows), enc1 never is
+    allowed = {POOL_PATHS[1]} | {pool_path(c, j, 1) for j in range(4)}
+    assert {p for p in POOL_PATHS if paths[p]} == allowed, f"{c.name}: pool paths run {dict(paths)}, the rule allows {sorted(allowed)}"
 
 
 # ------------------------------------------------------------------ more than two condition rows per image

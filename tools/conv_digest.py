@@ -2,8 +2,8 @@
 compute the same bits.
 
 The cases are those of tests/test_hip_conv_blocks.py (size factors 1.0 / 0.5 / 0.3 / 0.4, 16 px with 41 images -- ragged
-tiles down to M = 82 at 1x1 --, 32 px with 5 images, the mixed batch, the one-pass batch), with its enumeration of the
-admissible (tile, split, fuse) pins.  Per case:
+tiles down to M = 82 at 1x1 --, 32 px with 5 images, the mixed batch, the one-pass batch, and the rectangular pictures
+16 x 48, 48 x 16, 16 x 112, 32 x 48 and 16 x 80), with its enumeration of the admissible (tile, split, fuse) pins.  Per case:
 
   * one line per (block, slot, kind in fp32 / split-bf16 / strip): the block output and eps of every admissible pin of that
     slot with that kind, folded into one hash in the sorted order of the pins (head fusion off);
@@ -53,7 +53,7 @@ def line(name, digest, n):
 def case_lines(c):
     run = blocks.Runner(c, state_dict(c.sf))
     h = run.h
-    h.ensure_plan(run.rows, c.H, c.H, c.B, c.single, tune=False)
+    h.ensure_plan(run.rows, c.H, c.W, c.B, c.single, tune=False)
     found = run.admissible()
     groups = defaultdict(list)
     for key in sorted(found):
