@@ -136,6 +136,14 @@ TSNE_SIGNATURES = {
     "dt_tsne_descend": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
+# name -> (restype, argtypes) of every symbol include/dt_hip_quality.h declares (KID, precision / recall, density / coverage)
+QUALITY_SIGNATURES = {
+    "dt_quality_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dt_quality_scores": (c_int, [c_void_p, c_int, c_longlong, c_longlong, c_void_p, c_int, c_longlong, c_longlong, c_int,
+                                  c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_size_t, c_void_p, c_void_p]),
+}
+
 
 class TsneParams(ctypes.Structure):
     """dt_tsne_params of include/dt_hip_tsne.h"""
@@ -160,7 +168,7 @@ def load(path=None):
     except OSError as e:
         raise HipLibraryError(f"cannot load {path}: {e}. There is no CPU fallback.") from e
     for name, (res, args) in {**SIGNATURES, **NOISE_SIGNATURES, **INCEPTION_SIGNATURES, **PCA_SIGNATURES,
-                              **FID_SIGNATURES, **LPIPS_SIGNATURES, **TSNE_SIGNATURES}.items():
+                              **FID_SIGNATURES, **LPIPS_SIGNATURES, **TSNE_SIGNATURES, **QUALITY_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

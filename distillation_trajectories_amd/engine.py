@@ -897,14 +897,26 @@ FID_MAX_ROWS = 32768
 FID_EVENTS = 5
 
 
-def _fid_check(a, b):
+def _set_pair(a, b):
+    """the two feature sets of device_fid / device_quality: float32, [n, D] or [P, n, D], one width, one problem count"""
     a, b = (_f32_rows(t, name, "[n, D] or [P, n, D]") for t, name in ((a, "a"), (b, "b")))
     if a.shape[-1] != b.shape[-1]:
         raise ValueError(f"b {tuple(b.shape)} does not match a {tuple(a.shape)}: both sets need the same feature width")
     if a.dim() == 3 and b.dim() == 3 and a.shape[0] != b.shape[0]:
         raise ValueError(f"b {tuple(b.shape)} does not match a {tuple(a.shape)}: the same number of problems, or one "
                          "2-D set shared by all of them")
-    P = a.shape[0] if a.dim() == 3 else (b.shape[0] if b.dim() == 3 else 1)
+    return a, b, a.shape[0] if a.dim() == 3 else (b.shape[0] if b.dim() == 3 else 1)
+
+
+def _batch_limits(P, D):
+    if not 1 <= P <= 65535:
+        raise ValueError(f"unsupported number of problems P={P}")
+    if D < 4 or D % 4 or D > (1 << 20):
+        raise ValueError(f"the feature width must be a multiple of 4 in [4, 2^20], got D={D}")
+
+
+def _fid_check(a, b):
+    a, b, P = _set_pair(a, b)
     n_a, n_b, D = a.shape[-2], b.shape[-2], a.shape[-1]
     if n_a < 2 or n_b < 2:
         raise ValueError(f"a Fréchet distance needs at least 2 samples per set, got n_a={n_a}, n_b={n_b}")
@@ -912,10 +924,7 @@ def _fid_check(a, b):
         raise ValueError(f"n_a={n_a}, n_b={n_b}: the device Fréchet distance takes min(n_a, n_b) <= {FID_MAX_SIDE} (and at "
                          f"most {FID_MAX_ROWS} per set); with more samples than that in both sets the rank is capped by "
                          "the feature width and the feature-space formula (calculate_fid on the host) is the right one")
-    if not 1 <= P <= 65535:
-        raise ValueError(f"unsupported number of problems P={P}")
-    if D < 4 or D % 4 or D > (1 << 20):
-        raise ValueError(f"the feature width must be a multiple of 4 in [4, 2^20], got D={D}")
+    _batch_limits(P, D)
     return a, b, P
 
 
@@ -961,6 +970,109 @@ def device_fid(a, b, events=None, workspace=None):
         check(lib.dt_fid_distance(ptr(a), n_a, a_ps, a_rs, ptr(b), n_b, b_ps, b_rs, P, D, ptr(out["fid"]),
                                   ptr(out["parts"]), ptr(out["status"]), ptr(ws), ws_bytes, ev, stream_ptr()),
               "dt_fid_distance")
+    return out
+
+
+# ---------------------------------------------------------------------- KID, precision / recall, density / coverage
+# (include/dt_hip_quality.h)
+QUALITY_MAX_ROWS = 2048
+QUALITY_MAX_SUBSETS = 1024
+QUALITY_EVENTS = 5
+
+
+def _quality_check(a, b, k):
+    a, b, P = _set_pair(a, b)
+    for t, name in ((a, "a"), (b, "b")):
+        if not 2 <= t.shape[-2] <= QUALITY_MAX_ROWS:
+            raise ValueError(f"{name} holds {t.shape[-2]} rows: the device sample-quality scores take 2 .. "
+                             f"{QUALITY_MAX_ROWS} per set")
+    _batch_limits(P, a.shape[-1])
+    n_min = min(a.shape[-2], b.shape[-2])
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= n_min - 1:
+        raise ValueError(f"k={k!r} must be an integer in [1, min(n_a, n_b) - 1] = [1, {n_min - 1}]")
+    return a, b, P
+
+
+def _quality_subsets(subsets, n_a, n_b):
+    """(idx_a, idx_b) -> two int32 host arrays [S, m], range and distinctness per row checked"""
+    if not isinstance(subsets, (tuple, list)) or len(subsets) != 2:
+        raise ValueError("subsets must be a pair (idx_a, idx_b) of integer tables [S, m]")
+    tables = []
+    for t, n, name in ((subsets[0], n_a, "subsets[0]"), (subsets[1], n_b, "subsets[1]")):
+        t = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+        if t.ndim != 2 or not np.issubdtype(t.dtype, np.integer):
+            raise ValueError(f"{name} must be an integer table [S, m], got shape {t.shape}, dtype {t.dtype}")
+        if t.size and (t.min() < 0 or t.max() >= n):
+            raise ValueError(f"{name} holds an index outside [0, {n})")
+        s = np.sort(t, axis=1)
+        if np.any(s[:, 1:] == s[:, :-1]):
+            raise ValueError(f"{name} repeats an index within a row: the rows of a subset are distinct")
+        tables.append(np.ascontiguousarray(t, dtype=np.int32))
+    if tables[0].shape != tables[1].shape:
+        raise ValueError(f"subsets[1] {tables[1].shape} does not match subsets[0] {tables[0].shape}")
+    S, m = tables[0].shape
+    if not 1 <= S <= QUALITY_MAX_SUBSETS or not 2 <= m <= min(n_a, n_b):
+        raise ValueError(f"subsets: {S} subsets of size {m}; 1 .. {QUALITY_MAX_SUBSETS} subsets of size 2 .. "
+                         f"min(n_a, n_b) = {min(n_a, n_b)}")
+    return tables
+
+
+def device_quality(a, b, k=5, subsets=None, radii=False, events=None, workspace=None):
+    """KID, improved precision / recall and density / coverage between the feature sets a (the "real" set, the teacher) and
+    b (the "generated" set, a student), fp32 on the device: [n, D], or [P, n, D] for P problems; a 2-D set next to a 3-D
+    one is shared by all P problems.  All arithmetic is fp64 on the device (dt_quality_scores, whose header holds the
+    definitions): the Gram matrices, the squared k-th nearest-neighbour radii (self included, as ``prdc`` counts),
+    integer counts with strict ``<``, and the unbiased KID with the kernel ``(x.y / D + 1)^3``.  ``subsets``: None, or
+    ``(idx_a, idx_b)`` int tables [S, m] of distinct row numbers per row; each gives one more KID, of those rows.
+    Returns device tensors {kid [P] fp64, kid_subsets [P, S] fp64, counts [P, 4] int64 = (precision hits, recall hits,
+    density pairs, coverage hits), precision, recall, density, coverage [P] fp64 = counts / (n_b, n_a, k n_b, n_a),
+    status [P] int32 (0 ok, 1 a NaN or Inf in either set: the doubles are NaN, the counts -1)} and, with ``radii``,
+    radii_a [P, n_a] and radii_b [P, n_b] fp64 (squared).  Limits: 2 .. 2048 rows per set, D % 4 == 0,
+    1 <= k <= min(n_a, n_b) - 1.  ``events``: None or 5 torch.cuda.Event(enable_timing=True) recorded at the stage
+    boundaries.  ``workspace``: None (one is allocated) or a uint8 device tensor of at least
+    ``dt_quality_workspace_bytes`` bytes; its contents do not matter."""
+    a, b, P = _quality_check(a, b, k)
+    n_a, n_b, D = a.shape[-2], b.shape[-2], a.shape[-1]
+    tables = None if subsets is None else _quality_subsets(subsets, n_a, n_b)
+    if events is not None and len(events) != QUALITY_EVENTS:
+        raise ValueError(f"events must be {QUALITY_EVENTS} torch.cuda.Event")
+    _require_cuda(a, "a")
+    _require_cuda(b, "b")
+    if a.device != b.device:
+        raise ValueError(f"a is on {a.device}, b on {b.device}")
+    lib = _hip.load()
+    (a, a_ps, a_rs), (b, b_ps, b_rs) = _fid_rows(a), _fid_rows(b)
+    dev = a.device
+    S, m = (0, 0) if tables is None else tables[0].shape
+    f64 = dict(dtype=torch.float64, device=dev)
+    kid = torch.empty(P, 1 + S, **f64)
+    counts = torch.empty(P, 4, dtype=torch.int64, device=dev)
+    status = torch.empty(P, dtype=torch.int32, device=dev)
+    r2 = torch.empty(P, n_a + n_b, **f64) if radii else None
+    ws_bytes = lib.dt_quality_workspace_bytes(P, n_a, n_b, D)
+    if ws_bytes == 0:
+        raise ValueError(f"dt_quality_workspace_bytes rejects P={P}, n_a={n_a}, n_b={n_b}, D={D}")
+    with torch.cuda.device(dev):
+        sub = (None, None) if tables is None else tuple(torch.from_numpy(t).to(dev) for t in tables)
+        ev = _stage_events(events)
+        ws = workspace
+        if ws is None:
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        elif ws.dtype != torch.uint8 or ws.device != dev or not ws.is_contiguous() or ws.numel() < ws_bytes:
+            raise ValueError(f"workspace must be a contiguous uint8 tensor of >= {ws_bytes} bytes on {dev}")
+        check(lib.dt_quality_scores(ptr(a), n_a, a_ps, a_rs, ptr(b), n_b, b_ps, b_rs, P, D, int(k), ptr(sub[0]),
+                                    ptr(sub[1]), S, m, ptr(kid), ptr(counts), ptr(r2), ptr(status), ptr(ws), ws_bytes, ev,
+                                    stream_ptr()), "dt_quality_scores")
+        c = counts.to(torch.float64)
+        bad = counts[:, 0] < 0
+        out = {"kid": kid[:, 0], "kid_subsets": kid[:, 1:], "counts": counts, "status": status}
+        for name, col, den in (("precision", 0, n_b), ("recall", 1, n_a), ("density", 2, int(k) * n_b),
+                               ("coverage", 3, n_a)):
+            # a tensor divisor: torch divides by a Python scalar on the device as a product with its reciprocal
+            out[name] = torch.where(bad, torch.full_like(c[:, col], float("nan")),
+                                    c[:, col] / torch.full_like(c[:, col], float(den)))
+        if radii:
+            out["radii_a"], out["radii_b"] = r2[:, :n_a], r2[:, n_a:]
     return out
 
 
