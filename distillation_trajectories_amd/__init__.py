@@ -7,6 +7,7 @@ Public surface mirrors the reference's module paths:
   distillation_trajectories_amd.analysis.metrics.trajectory_metrics
   distillation_trajectories_amd.utils.trajectory_manager
   distillation_trajectories_amd.utils.metric_transformations
+  distillation_trajectories_amd.editing.{masked_inpainting,latent_manipulation,prompt_editing}   <- editing/
 Device work is done by csrc/ (hand-written HIP behind the C-ABI in include/dt_hip.h).
 """
 __version__ = "0.1.0"
@@ -27,6 +28,9 @@ _ALIASES = {
     "analysis.dimensionality.dimensionality_reduction": "analysis.dimensionality.dimensionality_reduction",
     "analysis.dimensionality.latent_space": "analysis.dimensionality.latent_space",
     "evaluation.metrics": "evaluation.metrics",
+    "editing.masked_inpainting": "editing.masked_inpainting",
+    "editing.latent_manipulation": "editing.latent_manipulation",
+    "editing.prompt_editing": "editing.prompt_editing",
 }
 
 

@@ -144,6 +144,21 @@ QUALITY_SIGNATURES = {
                                   c_void_p, c_size_t, c_void_p, c_void_p]),
 }
 
+# name -> (restype, argtypes) of every symbol include/dt_hip_edit.h declares (the editing stage: masked loops, hole statistics)
+EDIT_SIGNATURES = {
+    "dt_edit_start": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                              c_int, c_void_p]),
+    "dt_cfg_update_masked": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_float), c_int,
+                                     c_void_p, c_float, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p]),
+    "dt_sample_trajectory_masked": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,
+                                            POINTER(c_float), POINTER(c_int32), c_void_p, c_void_p, POINTER(c_int64),
+                                            c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_size_t, c_void_p]),
+    "dt_masked_pair_stats": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p]),
+}
+
 
 class TsneParams(ctypes.Structure):
     """dt_tsne_params of include/dt_hip_tsne.h"""
@@ -168,7 +183,7 @@ def load(path=None):
     except OSError as e:
         raise HipLibraryError(f"cannot load {path}: {e}. There is no CPU fallback.") from e
     for name, (res, args) in {**SIGNATURES, **NOISE_SIGNATURES, **INCEPTION_SIGNATURES, **PCA_SIGNATURES,
-                              **FID_SIGNATURES, **LPIPS_SIGNATURES, **TSNE_SIGNATURES, **QUALITY_SIGNATURES}.items():
+                              **FID_SIGNATURES, **LPIPS_SIGNATURES, **TSNE_SIGNATURES, **QUALITY_SIGNATURES, **EDIT_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -29,7 +29,14 @@ def extract(a, t, x_shape):
 def engine_coefficients(timesteps):
     """[(c1, c2, sigma)] for t = 0..T-1 from the per-step alphas = 1 - betas (reference :49, :97-110),
     formed with the same fp32 torch ops; row 0 is unused (x is recorded unchanged at t == 0)."""
-    alphas = 1.0 - get_diffusion_params(timesteps)["betas"].cpu()
+    return engine_coefficients_from_alphas(1.0 - get_diffusion_params(timesteps)["betas"].cpu(), timesteps)
+
+
+def engine_coefficients_from_alphas(alphas, timesteps=None):
+    """``engine_coefficients`` for a given table of per-step alphas (the editing modules read it from
+    ``diffusion_params["alphas"]``): rows for t = 0 .. timesteps-1 (default: the table's length)."""
+    alphas = alphas.detach().cpu()
+    timesteps = len(alphas) if timesteps is None else timesteps
     rows = [(1.0, 0.0, 0.0)]
     for t in range(1, timesteps):
         a_t, a_p = alphas[t], alphas[t - 1]

@@ -54,6 +54,7 @@ struct FusedArgs {
   const float *z;                      // LOOP: noise rows
   const int32_t *z_row;
   const float *wg;                     // per-image guidance scale (nullptr: w_scalar)
+  MaskArgs mk;                         // LOOP: known-region blend after every update (mk.mask == nullptr: none)
   long long z_shift[kFusedMaxSteps];
   float coef[kFusedMaxSteps][3];
   unsigned long long noise_mask;       // bit i: step i adds noise

@@ -366,6 +366,9 @@ __device__ __forceinline__ float eps_at_lds(int low, int c, int y, int x) {
 
 // mode FUSED_FORWARD: eps[r] = U-Net(x[image of row r]) for the batch rows blockIdx.x * G .. + G - 1
 // mode FUSED_LOOP:    the workgroup's images are advanced n_steps timesteps in place (trajectory slots in global memory)
+// MASKED (LOOP mode only): the known-region blend of the editing loops follows every update.  It is a second instantiation so
+// that the plain kernel stays the code it was (the blend's extra live values cost the shared body registers otherwise).
+template <bool MASKED>
 __global__ __launch_bounds__(kThreads, 4) void unet_fused_kernel(const FusedArgs a, const FusedOp *__restrict__ ops) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -508,8 +511,23 @@ __global__ __launch_bounds__(kThreads, 4) void unet_fused_kernel(const FusedArgs
         }
         o = (a.rule != DT_RULE_PSAMPLE && !noise) ? step1_rt(a.rule, xv, ev, 0.f, k3, false) : step1_rt(a.rule, xv, ev, zv[r], k3, noise);
       }
-      next[(size_t)b * E + e] = o;
+      if (!MASKED || dead) next[(size_t)b * E + e] = o;
       sm[L.x + k * kXSlot + e] = o;
+    }
+    if (MASKED && !dead) {
+      // the blend, as a pass of its own over the thread's elements (x' comes back from LDS: the update above keeps its
+      // register budget).  mask and known do not change from step to step; they are re-read here (L2 hits after the first
+      // step) and not held across the layers.  The ENGINE step at t == 0 records x unblended, as cfg_update_kernel does.
+#pragma unroll
+      for (int r = 0; r < kUpd; ++r) {
+        const int i = tid + r * kThreads;
+        if (i >= n_img * E) continue;
+        const int k = i / E, e = i - k * E, b = img0 + k;
+        const int mr = a.mk.mask_row ? a.mk.mask_row[b] : b, kr = a.mk.known_row ? a.mk.known_row[b] : b;
+        const float o = mask_blend(a.mk.mask[(size_t)mr * E + e], sm[L.x + k * kXSlot + e], a.mk.known[(size_t)kr * E + e]);
+        next[(size_t)b * E + e] = o;
+        sm[L.x + k * kXSlot + e] = o;
+      }
     }
     if (st + 1 < n_iter) load_tb(st + 1);           // (every layer of this step is behind a barrier: the rows are free)
     __syncthreads();
@@ -698,12 +716,15 @@ int launch_unet_fused(const FusedArgs &a, hipStream_t s) {
   {
     std::lock_guard<std::mutex> lock(attr_mu);
     if (attr_status[dev] == 0) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&unet_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&unet_fused_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&unet_fused_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       attr_status[dev] = e == hipSuccess ? 1 : -(int)e;
     }
     if (attr_status[dev] != 1) return -attr_status[dev];
   }
   if (a.G != 2 || a.n_ops < 1 || !a.ops) return DT_E_ARG;      // (the kernel's update slots per thread are sized for G = 2)
+  if (a.mk.mask && (!a.mk.known || a.mode != FUSED_LOOP)) return a.mk.known ? DT_E_ARG : DT_E_NULL;
   if (a.mode == FUSED_LOOP && (a.n_steps < 1 || a.n_steps > kFusedMaxSteps)) return DT_E_ARG;
   const size_t lds = (size_t)a.lds.total * sizeof(float);
   if (lds > 160 * 1024) return DT_E_SHAPE;
@@ -717,7 +738,8 @@ int launch_unet_fused(const FusedArgs &a, hipStream_t s) {
   }
   const int steps = a.mode == FUSED_FORWARD ? 1 : a.n_steps;
   ProfileScope prof(KC_FUSED, a.flops_per_row * Bt * steps, 4.0 * a.B * a.C * 256 * (steps + 1.0), s);
-  unet_fused_kernel<<<grid, kThreads, lds, s>>>(a, a.ops);
+  if (a.mk.mask) unet_fused_kernel<true><<<grid, kThreads, lds, s>>>(a, a.ops);
+  else unet_fused_kernel<false><<<grid, kThreads, lds, s>>>(a, a.ops);
   DT_LAUNCH_CHECK();
   return DT_OK;
 }

@@ -192,10 +192,19 @@ int launch_head(const float *lo, const float *w, const float *bias, float *lowre
                 hipStream_t s);
 int launch_head_upsample(const float *lowres, float *eps, int Bt, int h, int w_, int C, hipStream_t s);
 int launch_pack_res3(const float *w, const float *b, float *w3, int cout, int C, int n_p, hipStream_t s);
+// Known-region blend of a masked reverse step (include/dt_hip_edit.h): image b reads row mask_row[b] of mask[.][E] and row
+// known_row[b] of known[.][E] (a null table: row b).  mask == nullptr: no blend.
+struct MaskArgs {
+  const float *mask;
+  const int32_t *mask_row;
+  const float *known;
+  const int32_t *known_row;
+};
 // one reverse step with the prediction taken from the low-resolution head outputs of the passes (dt_update.hip)
 int launch_cfg_update_lowres(int rule, const float *x, const float *lowres_u, const float *lowres_c, const float *z,
                              const int32_t *z_row, long long z_shift, const float coef[4], int has_noise, const float *w,
-                             float w_scalar, float *out, int B, int C, int H, int W, int b_single, hipStream_t s);
+                             float w_scalar, float *out, int B, int C, int H, int W, int b_single, hipStream_t s,
+                             const MaskArgs &mk = MaskArgs{});
 
 struct TembWeights {
   const float *freqs;  // [half]

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "dt_fused.h"
+#include "../../include/dt_hip_edit.h"
 #include "dt_internal.h"
 
 using namespace dt;
@@ -908,6 +909,7 @@ struct SampleArgs {
   void *ws;
   size_t ws_bytes;
   hipStream_t s;
+  MaskArgs mk{};      // the masked entry only (dt_sample_trajectory_masked): known-region blend after every update
 };
 
 static int sample_loop(const dt_unet *h, const SampleArgs &a) {
@@ -928,6 +930,7 @@ static int sample_loop(const dt_unet *h, const SampleArgs &a) {
       fused_common(h, fa, B, a.n_pass, a.B_single, a.tb + (size_t)i0 * tb_rows * h->tb_stride, a.tb_div);
       fa.mode = FUSED_LOOP; fa.rule = a.rule; fa.n_steps = n;
       fa.traj = a.traj + (size_t)i0 * slot; fa.z = a.z; fa.z_row = a.z_row; fa.wg = a.w; fa.w_scalar = a.w_scalar;
+      fa.mk = a.mk;                                  // (travels with every launch of a loop longer than kFusedMaxSteps)
       for (int i = 0; i < n; ++i) {
         fa.coef[i][0] = a.coef[4 * (i0 + i)]; fa.coef[i][1] = a.coef[4 * (i0 + i) + 1]; fa.coef[i][2] = a.coef[4 * (i0 + i) + 2];
         fa.z_shift[i] = a.z_shift ? (long long)a.z_shift[i0 + i] : 0;
@@ -952,7 +955,7 @@ static int sample_loop(const dt_unet *h, const SampleArgs &a) {
     // second-pass rows start at row B and belong to images B_single .. B-1: indexed by image through a pointer shifted back
     int st = launch_cfg_update_lowres(a.rule, x, lowres, a.n_pass == 2 ? lowres + (size_t)(B - a.B_single) * (H / 2) * (W / 2) * 4 : nullptr, a.z,
                                       a.z_row, a.z_shift ? (long long)a.z_shift[i] : 0, a.coef + 4 * i, a.has_noise[i], a.w, a.w_scalar, xn,
-                                      B, h->desc.channels, H, W, a.B_single, a.s);
+                                      B, h->desc.channels, H, W, a.B_single, a.s, a.mk);
     if (st) return st;
   }
   return DT_OK;
@@ -1014,6 +1017,27 @@ int dt_sample_trajectory_mixed(const dt_unet *h, int rule, int B, int B_single, 
   if ((2 * B - B_single) % tb_div || B_single % tb_div || !h->share_enc1) return DT_E_ARG;   // a time-bias row never straddles the single / CFG boundary
   return sample_loop(h, SampleArgs{rule, B, 2, B_single, H, W, n_steps, tb, tb_div, coef, has_noise, z, z_row, z_shift, w, 1.f, traj, ws, ws_bytes,
                                    (hipStream_t)stream});
+}
+
+// The masked loop of the editing stage (include/dt_hip_edit.h).  Always plain launches: it takes no part in the opt-in graph replay.
+int dt_sample_trajectory_masked(const dt_unet *h, int rule, int B, int n_pass, int B_single, int H, int W, int n_steps,
+                                const float *tb, int tb_div, const float *coef, const int32_t *has_noise, const float *z,
+                                const int32_t *z_row, const int64_t *z_shift, const float *w, float w_scalar, const float *mask,
+                                const int32_t *mask_row, const float *known, const int32_t *known_row, float *traj, void *ws,
+                                size_t ws_bytes, void *stream) {
+  if (!h || !tb || !coef || !has_noise || !traj || !ws || !mask || !known) return DT_E_NULL;
+  if (n_pass < 1 || n_pass > 2 || n_steps < 0 || rule < 0 || rule > DT_RULE_MANAGER || tb_div < 1) return DT_E_ARG;
+  if (B < 1 || B_single < 0 || B_single > B || (n_pass == 1 && B_single)) return DT_E_ARG;
+  if (B_single == B) { n_pass = 1; B_single = 0; }                       // every image takes one pass
+  if (B_single) {                                                        // a mixed batch: dt_sample_trajectory_mixed's conditions
+    if (!w) return DT_E_NULL;
+    if ((2 * B - B_single) % tb_div || B_single % tb_div || !h->share_enc1) return DT_E_ARG;
+  }
+  if (((uintptr_t)mask | (uintptr_t)known | (uintptr_t)traj) & 15) return DT_E_ARG;   // float4 reads of the layered update
+  SampleArgs a{rule, B, n_pass, B_single, H, W, n_steps, tb, tb_div, coef, has_noise, z, z_row, z_shift, w, w_scalar, traj, ws, ws_bytes,
+               (hipStream_t)stream};
+  a.mk = MaskArgs{mask, mask_row, known, known_row};
+  return sample_loop(h, a);
 }
 
 int dt_unet_forward_mixed(const dt_unet *h, const float *x, int B, int B_single, int H, int W, const float *tb, int tb_div,

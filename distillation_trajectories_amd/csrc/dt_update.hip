@@ -5,6 +5,8 @@
 //   ENGINE : x' = c1*x - c2*eps ; x' += sigma*z       trajectory_engine.py:104-110
 //   PSAMPLE: x' = sra*(x - k*eps) + z*beta            utils/diffusion.py:149-158
 //   MANAGER: x' = (x - b*eps)/sqrt(a) ; x' += s*z     utils/trajectory_manager.py:196-203
+// the masked form of the editing loops, which keeps the known region after the rule:
+//   out = m*x' + (1 - m)*known                        editing/masked_inpainting.py:218
 // and the forward noising of the noise-prediction analysis (q_sample_kernel below):
 //   x_t = sqrt(ab_t)*x0 + sqrt(1-ab_t)*z              analysis/noise_prediction/noise_analysis.py:268
 // x' is written straight into the next trajectory slot (which is the next step's input), so the
@@ -14,6 +16,7 @@
 // (HIP's __fmul_rn/__fadd_rn are header inlines compiled with contraction on, so they are not used.)
 #include "dt_update_math.h"
 #include "../../include/dt_hip_noise.h"
+#include "../../include/dt_hip_edit.h"
 
 #pragma clang fp contract(off)
 
@@ -33,6 +36,7 @@ struct UpdateArgs {
   int has_noise, B, E4;
   int lh, lw, hw;
   int b_single;        // rows [0, b_single) take the first prediction as it is (single-pass images of a mixed batch)
+  MaskArgs mk;         // MASKED kernels only
 };
 
 // eps of element (b, c, y, x..x+3) from a low-resolution head output (same arithmetic as head_upsample_kernel)
@@ -57,7 +61,7 @@ __device__ inline float4 eps_from_lowres(const float *lowres, int b, int e, cons
   return make_float4(r[0], r[1], r[2], r[3]);
 }
 
-template <int RULE, bool LOWRES = false>
+template <int RULE, bool LOWRES = false, bool MASKED = false>
 __global__ __launch_bounds__(256) void cfg_update_kernel(const UpdateArgs a) {
   const size_t total = (size_t)a.B * a.E4;
   const float4 *x4 = reinterpret_cast<const float4 *>(a.x);
@@ -78,6 +82,11 @@ __global__ __launch_bounds__(256) void cfg_update_kernel(const UpdateArgs a) {
       ev.z = ev.z + w * (cv.z - ev.z);
       ev.w = ev.w + w * (cv.w - ev.w);
     }
+    float4 mv, kv;
+    if (MASKED) {      // requested ahead of the arithmetic, like the noise below
+      mv = reinterpret_cast<const float4 *>(a.mk.mask)[(size_t)(a.mk.mask_row ? a.mk.mask_row[b] : b) * a.E4 + e];
+      kv = reinterpret_cast<const float4 *>(a.mk.known)[(size_t)(a.mk.known_row ? a.mk.known_row[b] : b) * a.E4 + e];
+    }
     float4 zv = make_float4(0.f, 0.f, 0.f, 0.f);
     const bool noise = a.has_noise != 0;
     if (noise) {
@@ -93,30 +102,64 @@ __global__ __launch_bounds__(256) void cfg_update_kernel(const UpdateArgs a) {
       o.x = step1<RULE>(xv.x, ev.x, zv.x, a.k, noise); o.y = step1<RULE>(xv.y, ev.y, zv.y, a.k, noise);
       o.z = step1<RULE>(xv.z, ev.z, zv.z, a.k, noise); o.w = step1<RULE>(xv.w, ev.w, zv.w, a.k, noise);
     }
+    if (MASKED) {
+      o.x = mask_blend(mv.x, o.x, kv.x); o.y = mask_blend(mv.y, o.y, kv.y);
+      o.z = mask_blend(mv.z, o.z, kv.z); o.w = mask_blend(mv.w, o.w, kv.w);
+    }
     o4[i] = o;
   }
+}
+
+template <bool LOWRES>
+static int launch_update(int rule, const UpdateArgs &a, int blocks, hipStream_t s) {
+  const bool masked = a.mk.mask != nullptr;
+  switch (rule) {
+    case DT_RULE_ENGINE:
+      if (masked) cfg_update_kernel<DT_RULE_ENGINE, LOWRES, true><<<blocks, 256, 0, s>>>(a);
+      else cfg_update_kernel<DT_RULE_ENGINE, LOWRES><<<blocks, 256, 0, s>>>(a);
+      break;
+    case DT_RULE_PSAMPLE:
+      if (masked) cfg_update_kernel<DT_RULE_PSAMPLE, LOWRES, true><<<blocks, 256, 0, s>>>(a);
+      else cfg_update_kernel<DT_RULE_PSAMPLE, LOWRES><<<blocks, 256, 0, s>>>(a);
+      break;
+    case DT_RULE_MANAGER:
+      if (masked) cfg_update_kernel<DT_RULE_MANAGER, LOWRES, true><<<blocks, 256, 0, s>>>(a);
+      else cfg_update_kernel<DT_RULE_MANAGER, LOWRES><<<blocks, 256, 0, s>>>(a);
+      break;
+    default: return DT_E_ARG;
+  }
+  DT_LAUNCH_CHECK();
+  return DT_OK;
+}
+
+static int update_flat(int rule, const float *x, const float *eu, const float *ec, const float *z, const int32_t *z_row,
+                       const float coef[4], int has_noise, const float *w, float w_scalar, float *out, int B, int E,
+                       const MaskArgs &mk, hipStream_t s) {
+  if (!x || !eu || !out || !coef) return DT_E_NULL;
+  if (has_noise && !z) return DT_E_NULL;
+  if (B <= 0 || E <= 0 || E % 4) return DT_E_SHAPE;
+  UpdateArgs a{x, eu, ec, z, z_row, w, out, {coef[0], coef[1], coef[2]}, w_scalar, 0, has_noise, B, E / 4, 0, 0, 0, 0, mk};
+  const size_t total = (size_t)B * (E / 4);
+  const int blocks = grid_blocks(total, 2048);
+  // algorithmic bytes: read x + read z + write x' = 3*E*4 per sample-step (+ eps reads, + mask and known)
+  ProfileScope prof(KC_UPDATE, 0.0, 4.0 * B * E * (2.0 + (has_noise ? 1.0 : 0.0) + (ec ? 2.0 : 1.0) + (mk.mask ? 2.0 : 0.0)), s);
+  return launch_update<false>(rule, a, blocks, s);
 }
 
 extern "C" int dt_cfg_update(int rule, const float *x, const float *eu, const float *ec, const float *z, const int32_t *z_row,
                              const float coef[4], int has_noise, const float *w, float w_scalar, float *out, int B, int E,
                              void *stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (!x || !eu || !out || !coef) return DT_E_NULL;
-  if (has_noise && !z) return DT_E_NULL;
-  if (B <= 0 || E <= 0 || E % 4) return DT_E_SHAPE;
-  UpdateArgs a{x, eu, ec, z, z_row, w, out, {coef[0], coef[1], coef[2]}, w_scalar, 0, has_noise, B, E / 4, 0, 0, 0, 0};
-  const size_t total = (size_t)B * (E / 4);
-  const int blocks = grid_blocks(total, 2048);
-  // algorithmic bytes: read x + read z + write x' = 3*E*4 per sample-step (+ eps reads)
-  ProfileScope prof(KC_UPDATE, 0.0, 4.0 * B * E * (2.0 + (has_noise ? 1.0 : 0.0) + (ec ? 2.0 : 1.0)), s);
-  switch (rule) {
-    case DT_RULE_ENGINE: cfg_update_kernel<DT_RULE_ENGINE><<<blocks, 256, 0, s>>>(a); break;
-    case DT_RULE_PSAMPLE: cfg_update_kernel<DT_RULE_PSAMPLE><<<blocks, 256, 0, s>>>(a); break;
-    case DT_RULE_MANAGER: cfg_update_kernel<DT_RULE_MANAGER><<<blocks, 256, 0, s>>>(a); break;
-    default: return DT_E_ARG;
-  }
-  DT_LAUNCH_CHECK();
-  return DT_OK;
+  return update_flat(rule, x, eu, ec, z, z_row, coef, has_noise, w, w_scalar, out, B, E, MaskArgs{}, (hipStream_t)stream);
+}
+
+extern "C" int dt_cfg_update_masked(int rule, const float *x, const float *eu, const float *ec, const float *z,
+                                    const int32_t *z_row, const float coef[4], int has_noise, const float *w, float w_scalar,
+                                    float *out, int B, int E, void *stream, const float *mask, const int32_t *mask_row,
+                                    const float *known, const int32_t *known_row) {
+  if (!mask || !known) return DT_E_NULL;
+  if (((uintptr_t)mask | (uintptr_t)known) & 15) return DT_E_ARG;   // float4 reads
+  return update_flat(rule, x, eu, ec, z, z_row, coef, has_noise, w, w_scalar, out, B, E, MaskArgs{mask, mask_row, known, known_row},
+                     (hipStream_t)stream);
 }
 
 // the same step with the prediction taken from the low-resolution head outputs of the two passes (lowres_u, lowres_c:
@@ -124,25 +167,20 @@ extern "C" int dt_cfg_update(int rule, const float *x, const float *eu, const fl
 // and lowres_c is indexed from image b_single on (the caller passes the second pass's first row shifted back by b_single images).
 int launch_cfg_update_lowres(int rule, const float *x, const float *lowres_u, const float *lowres_c, const float *z,
                              const int32_t *z_row, long long z_shift, const float coef[4], int has_noise, const float *w,
-                             float w_scalar, float *out, int B, int C, int H, int W, int b_single, hipStream_t s) {
+                             float w_scalar, float *out, int B, int C, int H, int W, int b_single, hipStream_t s,
+                             const MaskArgs &mk) {
   if (!x || !lowres_u || !out || !coef) return DT_E_NULL;
+  if (mk.mask && (!mk.known || ((uintptr_t)mk.mask | (uintptr_t)mk.known) & 15)) return mk.known ? DT_E_ARG : DT_E_NULL;
   if (has_noise && !z) return DT_E_NULL;
   const int E = C * H * W;
   if (B <= 0 || E <= 0 || W % 4 || H % 2 || W % 2) return DT_E_SHAPE;
   if (b_single < 0 || b_single > B) return DT_E_ARG;
   UpdateArgs a{x, lowres_u, lowres_c, z, z_row, w, out, {coef[0], coef[1], coef[2]}, w_scalar, z_shift, has_noise, B, E / 4,
-               H / 2, W / 2, H * W, b_single};
+               H / 2, W / 2, H * W, b_single, mk};
   const size_t total = (size_t)B * (E / 4);
   const int blocks = grid_blocks(total, 2048);
-  ProfileScope prof(KC_UPDATE, 0.0, 4.0 * B * E * (2.0 + (has_noise ? 1.0 : 0.0)) + 4.0 * B * H * W * (lowres_c ? 2.0 : 1.0), s);
-  switch (rule) {
-    case DT_RULE_ENGINE: cfg_update_kernel<DT_RULE_ENGINE, true><<<blocks, 256, 0, s>>>(a); break;
-    case DT_RULE_PSAMPLE: cfg_update_kernel<DT_RULE_PSAMPLE, true><<<blocks, 256, 0, s>>>(a); break;
-    case DT_RULE_MANAGER: cfg_update_kernel<DT_RULE_MANAGER, true><<<blocks, 256, 0, s>>>(a); break;
-    default: return DT_E_ARG;
-  }
-  DT_LAUNCH_CHECK();
-  return DT_OK;
+  ProfileScope prof(KC_UPDATE, 0.0, 4.0 * B * E * (2.0 + (has_noise ? 1.0 : 0.0) + (mk.mask ? 2.0 : 0.0)) + 4.0 * B * H * W * (lowres_c ? 2.0 : 1.0), s);
+  return launch_update<true>(rule, a, blocks, s);
 }
 
 // Forward noising q(x_t | x_0) of n_groups timestep groups in one launch      analysis/noise_prediction/noise_analysis.py:268

@@ -36,6 +36,16 @@ __device__ inline float step1_rt(int rule, float x, float eps, float z, const St
   return step1<DT_RULE_MANAGER>(x, eps, z, a, noise);
 }
 
+// known-region blend of the editing loops: out = m*x' + (1 - m)*known       editing/masked_inpainting.py:181,218
+// Two rounded products, the rounded 1 - m, one rounded sum: bit-identical to torch CPU for soft masks; m == 0 gives `known`
+// and m == 1 gives x' exactly (x' * 1 + known * 0, finite operands).
+__device__ inline float mask_blend(float m, float xn, float known) {
+#pragma clang fp contract(off)
+  const float a = m * xn;
+  const float b = (1.f - m) * known;
+  return a + b;
+}
+
 // eps = e_u + w (e_c - e_u)                            utils/diffusion.py:126, trajectory_engine.py:80
 __device__ inline float cfg_mix(float eu, float ec, float w) {
 #pragma clang fp contract(off)

@@ -455,6 +455,94 @@ class UNetHandle:
                   "dt_sample_trajectory")
         return traj
 
+    def sample_masked(self, rule, traj, H, W, tb, n_pass, coef, has_noise, mask, known, mask_row=None, known_row=None, z=None,
+                      z_row=None, z_shift=None, w=None, w_scalar=1.0, b_single=0, tb_div=None):
+        """``sample`` (``b_single`` > 0: ``sample_mixed``) with the known-region blend after every update
+        (dt_sample_trajectory_masked): row b of traj keeps ``known[known_row[b]]`` where ``mask[mask_row[b]]`` is 0.  mask and
+        known are fp32 device tensors [rows, E]; a row table that is None is the identity."""
+        _require_cuda(traj, "traj"); _require_cuda(mask, "mask"); _require_cuda(known, "known")
+        n_steps = len(coef)
+        B, E = traj.shape[1], traj.shape[2]
+        rows = n_pass * B - b_single * (n_pass - 1)
+        tb_div = B if tb_div is None else tb_div
+        assert traj.shape[0] == n_steps + 1 and traj.is_contiguous() and traj.dtype == torch.float32
+        for name, t, row in (("mask", mask, mask_row), ("known", known, known_row)):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != E:
+                raise HipLibraryError(f"sample_masked: {name} must be a contiguous float32 [rows, {E}] tensor, got {tuple(t.shape)} {t.dtype}")
+            if row is None and t.shape[0] < B:
+                raise HipLibraryError(f"sample_masked: {name} has {t.shape[0]} rows for {B} images and no row table")
+            if row is not None and (row.dtype != torch.int32 or row.numel() != B or not row.is_cuda):
+                raise HipLibraryError(f"sample_masked: {name}_row must be an int32 device tensor of {B} entries")
+        coef_c = (c_float * (4 * n_steps))(*[float(v) for row in coef for v in (list(row) + [0.0] * 4)[:4]])
+        noise_c = (c_int32 * n_steps)(*[int(bool(v)) for v in has_noise])
+        shift_c = (c_int64 * n_steps)(*[int(v) for v in (z_shift if z_shift is not None else [0] * n_steps)])
+        ws = self.workspace(rows, H, W)
+        if n_steps and self.shape(rows, H, W, B, b_single) not in self._plans:
+            x0 = traj[0].reshape(B, self.channels, H, W)
+            if b_single:
+                self.forward_mixed(x0, tb[:rows // tb_div].contiguous(), b_single, tb_div)
+            else:
+                self.forward(x0, tb[:rows // tb_div].contiguous(), n_pass, tb_div)
+        with torch.cuda.device(self.device):
+            check(self.lib.dt_sample_trajectory_masked(self.h, rule, B, n_pass, b_single, H, W, n_steps, ptr(tb), tb_div, coef_c,
+                                                       noise_c, ptr(z), ptr(z_row), shift_c, ptr(w), c_float(w_scalar),
+                                                       ptr(mask), ptr(mask_row), ptr(known), ptr(known_row), ptr(traj), ptr(ws),
+                                                       c_size_t(ws.numel()), stream_ptr()), "dt_sample_trajectory_masked")
+        return traj
+
+
+def cfg_update_masked(rule, x, eps_u, eps_c, z, coef, has_noise, mask, known, mask_row=None, known_row=None, w=None,
+                      w_scalar=1.0, z_row=None):
+    """``cfg_update`` followed by the known-region blend ``m * x' + (1 - m) * known`` (dt_cfg_update_masked); mask and known
+    are fp32 device tensors of rows of x[0].numel() elements, picked per image by the row tables (None: row b)."""
+    lib = _hip.load()
+    _require_cuda(x, "x"); _require_cuda(mask, "mask"); _require_cuda(known, "known")
+    B, E = x.shape[0], x[0].numel()
+    out = torch.empty_like(x)
+    coef_c = (c_float * 4)(*(list(coef) + [0.0] * 4)[:4])
+    with torch.cuda.device(x.device):
+        check(lib.dt_cfg_update_masked(rule, ptr(x), ptr(eps_u), ptr(eps_c), ptr(z), ptr(z_row), coef_c, int(bool(has_noise)),
+                                       ptr(w), c_float(w_scalar), ptr(out), B, E, stream_ptr(), ptr(mask), ptr(mask_row),
+                                       ptr(known), ptr(known_row)), "dt_cfg_update_masked")
+    return out
+
+
+def edit_start(images, z, mask, B, img_row=None, z_row=None, mask_row=None, x_out=None):
+    """(known [n_img, E], x [B, E]) of dt_edit_start: ``known = 2 * images - 1`` and the start states
+    ``x[b] = m * z[z_row[b]] + (1 - m) * known[img_row[b]]`` with ``m = mask[mask_row[b]]``.  images in [0, 1], z and mask
+    are fp32 device tensors of rows of E elements; ``x_out`` (e.g. slot 0 of a trajectory buffer) is written when given."""
+    lib = _hip.load()
+    _require_cuda(images, "images"); _require_cuda(z, "z"); _require_cuda(mask, "mask")
+    images, z, mask = (t.reshape(t.shape[0], -1).contiguous().float() for t in (images, z, mask))
+    n_img, E = images.shape
+    if z.shape[1] != E or mask.shape[1] != E:
+        raise HipLibraryError(f"edit_start: rows of {E} (images), {z.shape[1]} (z) and {mask.shape[1]} (mask) elements")
+    for name, t, row in (("images", images, img_row), ("z", z, z_row), ("mask", mask, mask_row)):
+        if row is None and t.shape[0] < B:
+            raise HipLibraryError(f"edit_start: {name} has {t.shape[0]} rows for {B} cells and no row table")
+    known = torch.empty_like(images)
+    x = torch.empty(B, E, dtype=torch.float32, device=images.device) if x_out is None else x_out
+    with torch.cuda.device(images.device):
+        check(lib.dt_edit_start(ptr(images), ptr(img_row), n_img, ptr(z), ptr(z_row), ptr(mask), ptr(mask_row), ptr(known),
+                                ptr(x), B, E, stream_ptr()), "dt_edit_start")
+    return known, x
+
+
+def device_masked_pair_stats(X, Y, mask, known, mask_row=None, known_row=None):
+    """float64 [B, n, 4] = {sum m (x-y)^2, sum m (x-k)^2, sum m (y-k)^2, sum (1-m) (x-y)^2} per state of X, Y [n, B, E]
+    (dt_masked_pair_stats; E % 4 == 0), m and k the mask / known rows of image b."""
+    lib = _hip.load()
+    _require_cuda(X, "X"); _require_cuda(Y, "Y"); _require_cuda(mask, "mask"); _require_cuda(known, "known")
+    X, Y = X.contiguous(), Y.contiguous()
+    n, B, E = X.shape
+    if tuple(Y.shape) != (n, B, E) or mask.shape[-1] != E or known.shape[-1] != E:
+        raise HipLibraryError(f"device_masked_pair_stats: X {tuple(X.shape)}, Y {tuple(Y.shape)}, mask {tuple(mask.shape)}, known {tuple(known.shape)}")
+    out = torch.empty(B, n, 4, dtype=torch.float64, device=X.device)
+    with torch.cuda.device(X.device):
+        check(lib.dt_masked_pair_stats(ptr(X), ptr(Y), n, B, E, ptr(mask.contiguous()), ptr(mask_row), ptr(known.contiguous()),
+                                       ptr(known_row), ptr(out), stream_ptr()), "dt_masked_pair_stats")
+    return out
+
 
 def cfg_update(rule, x, eps_u, eps_c, z, coef, has_noise, w=None, w_scalar=1.0, z_row=None):
     """One fused CFG-mix + update step (dt_cfg_update); returns the new x."""
