@@ -112,6 +112,12 @@ FID_SIGNATURES = {
                                 c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
 }
 
+# name -> (restype, argtypes) of every symbol include/dt_hip_fid_cov.h declares (the same distance by the feature-space route)
+FID_COV_SIGNATURES = {
+    "dt_fid_cov_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dt_fid_cov_distance": FID_SIGNATURES["dt_fid_distance"],
+}
+
 # name -> (restype, argtypes) of every symbol include/dt_hip_lpips.h declares (the perceptual distance)
 LPIPS_SIGNATURES = {
     "dt_lpips_create": (c_int, [POINTER(c_void_p), c_int, c_void_p, POINTER(c_void_p)]),
@@ -183,7 +189,7 @@ def load(path=None):
     except OSError as e:
         raise HipLibraryError(f"cannot load {path}: {e}. There is no CPU fallback.") from e
     for name, (res, args) in {**SIGNATURES, **NOISE_SIGNATURES, **INCEPTION_SIGNATURES, **PCA_SIGNATURES,
-                              **FID_SIGNATURES, **LPIPS_SIGNATURES, **TSNE_SIGNATURES, **QUALITY_SIGNATURES, **EDIT_SIGNATURES}.items():
+                              **FID_SIGNATURES, **FID_COV_SIGNATURES, **LPIPS_SIGNATURES, **TSNE_SIGNATURES, **QUALITY_SIGNATURES, **EDIT_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

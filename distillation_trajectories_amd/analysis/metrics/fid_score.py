@@ -13,7 +13,9 @@ with the user's copy of torchvision's pretrained weights (``weights=`` or ``DT_I
 ``calculate_and_visualize_fid`` is the reference's driver (:96-198) without the figure.
 
 ``stats="device"`` (or ``DT_FID_STATS=device``) keeps the features on the device and takes the Fréchet distance there
-too (``calculate_fid_device``, ``engine.device_fid``, include/dt_hip_fid.h): one double comes back.  The default,
+too (``calculate_fid_device``, ``engine.device_fid_auto``): one double comes back.  With at most 2048 samples in the
+smaller set that is the sample-space route (``engine.device_fid``, include/dt_hip_fid.h); with more in both sets, as FID is
+normally reported, the feature-space route (``engine.device_fid_cov``, include/dt_hip_fid_cov.h).  The default,
 ``"host"``, is the reference's numpy/scipy formula on the copied features.  ``fid_sweep`` scores several students against
 one teacher in one batched device call.
 """
@@ -54,9 +56,10 @@ def stats_mode(stats=None):
 
 
 def calculate_fid_device(features_1, features_2):
-    """``calculate_fid`` with the arithmetic on the device, in fp64 (``engine.device_fid``): fp32 features [N, D] that are
-    on the device already, or host tensors / arrays that are uploaded first; returns a Python float.  The same 999.0
-    placeholder below 2 samples.  At most 2048 samples in the smaller set; NaN if a feature is NaN or infinite."""
+    """``calculate_fid`` with the arithmetic on the device, in fp64 (``engine.device_fid_auto``): fp32 features [N, D] that
+    are on the device already, or host tensors / arrays that are uploaded first; returns a Python float.  The same 999.0
+    placeholder below 2 samples.  Up to 2048 samples in the smaller set go the sample-space route, longer sets (up to
+    131072 samples each, D <= 2048) the feature-space one (``engine.fid_route``); NaN if a feature is NaN or infinite."""
     if len(features_1) < 2 or len(features_2) < 2:
         print("  Warning: Not enough samples for a proper FID calculation.")
         print(f"  Number of samples in set 1: {len(features_1)}")
@@ -66,7 +69,7 @@ def calculate_fid_device(features_1, features_2):
     sets = [torch.as_tensor(f) for f in (features_1, features_2)]
     device = next((t.device for t in sets if t.is_cuda), torch.device("cuda"))
     sets = [t if t.is_cuda else t.to(device) for t in sets]
-    return float(engine.device_fid(sets[0], sets[1])["fid"][0])
+    return float(engine.device_fid_auto(sets[0], sets[1])["fid"][0])
 
 
 def posterior_coefficients(config):
@@ -200,9 +203,9 @@ def calculate_and_visualize_fid(teacher_model, student_model, config, output_dir
 def fid_sweep(teacher_model, student_models, config, num_samples, weights=None, fixed_samples=None):
     """FID of every student against one teacher: the teacher's samples and features once, each student's samples and
     features (``generate_samples`` in that order, so the CPU generator is consumed as by one
-    ``calculate_and_visualize_fid`` call for the teacher followed by the students), then one batched ``engine.device_fid``
-    with the teacher's features shared.  Returns numpy ``fid [n_students]`` and ``parts [n_students, 4]`` (float64) and
-    ``status [n_students]``; nothing else leaves the device."""
+    ``calculate_and_visualize_fid`` call for the teacher followed by the students), then one batched
+    ``engine.device_fid_auto`` with the teacher's features shared.  Returns numpy ``fid [n_students]`` and
+    ``parts [n_students, 4]`` (float64) and ``status [n_students]``; nothing else leaves the device."""
     student_models = list(student_models)
     if not student_models:
         raise ValueError("fid_sweep needs at least one student model")
@@ -218,5 +221,5 @@ def fid_sweep(teacher_model, student_models, config, num_samples, weights=None, 
 
     teacher = features(teacher_model)
     students = torch.stack([features(m) for m in student_models])
-    res = engine.device_fid(teacher, students)
+    res = engine.device_fid_auto(teacher, students)
     return {k: v.cpu().numpy() for k, v in res.items()}

@@ -18,6 +18,7 @@ HEADERS = ["dt_internal.h", "dt_conv_forms.h", "dt_dense64.h", "dt_featnet.h", "
            os.path.join("..", "..", "include", "dt_hip_inception.h"),
            os.path.join("..", "..", "include", "dt_hip_pca.h"),
            os.path.join("..", "..", "include", "dt_hip_fid.h"),
+           os.path.join("..", "..", "include", "dt_hip_fid_cov.h"),
            os.path.join("..", "..", "include", "dt_hip_lpips.h"),
            os.path.join("..", "..", "include", "dt_hip_tsne.h"),
            os.path.join("..", "..", "include", "dt_hip_quality.h"),

@@ -1032,8 +1032,13 @@ def device_fid(a, b, events=None, workspace=None):
     torch.cuda.Event(enable_timing=True) recorded at the stage boundaries (dt_fid_distance).  ``workspace``: None (one is
     allocated) or a uint8 device tensor of at least ``dt_fid_workspace_bytes`` bytes; its contents do not matter."""
     a, b, P = _fid_check(a, b)
-    if events is not None and len(events) != FID_EVENTS:
-        raise ValueError(f"events must be {FID_EVENTS} torch.cuda.Event")
+    return _fid_call(a, b, P, events, workspace, FID_EVENTS, "dt_fid_workspace_bytes", "dt_fid_distance")
+
+
+def _fid_call(a, b, P, events, workspace, n_events, query, entry):
+    """the checked sets through one of the two entries (they share the argument list) with that entry's workspace query"""
+    if events is not None and len(events) != n_events:
+        raise ValueError(f"events must be {n_events} torch.cuda.Event")
     _require_cuda(a, "a")
     _require_cuda(b, "b")
     if a.device != b.device:
@@ -1045,9 +1050,9 @@ def device_fid(a, b, events=None, workspace=None):
     out = {"fid": torch.empty(P, dtype=torch.float64, device=dev),
            "parts": torch.empty(P, 4, dtype=torch.float64, device=dev),
            "status": torch.empty(P, dtype=torch.int32, device=dev)}
-    ws_bytes = lib.dt_fid_workspace_bytes(P, n_a, n_b, D)
+    ws_bytes = getattr(lib, query)(P, n_a, n_b, D)
     if ws_bytes == 0:
-        raise ValueError(f"dt_fid_workspace_bytes rejects P={P}, n_a={n_a}, n_b={n_b}, D={D}")
+        raise ValueError(f"{query} rejects P={P}, n_a={n_a}, n_b={n_b}, D={D}")
     with torch.cuda.device(dev):
         ev = _stage_events(events)
         ws = workspace
@@ -1055,10 +1060,60 @@ def device_fid(a, b, events=None, workspace=None):
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         elif ws.dtype != torch.uint8 or ws.device != dev or not ws.is_contiguous() or ws.numel() < ws_bytes:
             raise ValueError(f"workspace must be a contiguous uint8 tensor of >= {ws_bytes} bytes on {dev}")
-        check(lib.dt_fid_distance(ptr(a), n_a, a_ps, a_rs, ptr(b), n_b, b_ps, b_rs, P, D, ptr(out["fid"]),
+        check(getattr(lib, entry)(ptr(a), n_a, a_ps, a_rs, ptr(b), n_b, b_ps, b_rs, P, D, ptr(out["fid"]),
                                   ptr(out["parts"]), ptr(out["status"]), ptr(ws), ws_bytes, ev, stream_ptr()),
-              "dt_fid_distance")
+              entry)
     return out
+
+
+# ---------------------------------------------------------------------- the feature-space route (include/dt_hip_fid_cov.h)
+FID_COV_MAX_ROWS = 131072
+FID_COV_MAX_WIDTH = 2048
+FID_COV_EVENTS = 7
+
+
+def _fid_cov_check(a, b):
+    a, b, P = _set_pair(a, b)
+    n_a, n_b, D = a.shape[-2], b.shape[-2], a.shape[-1]
+    if n_a < 2 or n_b < 2:
+        raise ValueError(f"a Fréchet distance needs at least 2 samples per set, got n_a={n_a}, n_b={n_b}")
+    _batch_limits(P, D)
+    if max(n_a, n_b) > FID_COV_MAX_ROWS or D > FID_COV_MAX_WIDTH:
+        raise ValueError(f"n_a={n_a}, n_b={n_b}, D={D}: the feature-space Fréchet distance on the device takes at most "
+                         f"{FID_COV_MAX_ROWS} samples per set and a feature width of at most {FID_COV_MAX_WIDTH}")
+    return a, b, P
+
+
+def device_fid_cov(a, b, events=None, workspace=None):
+    """``device_fid`` by the feature-space route (dt_fid_cov_distance): the same input forms and the same returned dict,
+    for sets of up to 131072 rows each and a feature width of at most 2048.  The cross term comes from the singular
+    values of ``L_a^T L_b``, with ``L`` the Cholesky factors of the two D x D centred covariance products (a pivot that is
+    not above D 2^-52 max diag gives a zero column), all in fp64 on the device and every sum in a fixed order.  Sets
+    shorter than D are legal, only slower than ``device_fid``; where both apply the two agree to rounding, not to the bit.
+    ``events``: None or 7 torch.cuda.Event(enable_timing=True) (start, means + traces, covariances, factors, N and its
+    square, tridiagonalisation, end).  ``workspace``: None or a uint8 device tensor of at least
+    ``dt_fid_cov_workspace_bytes`` bytes; its contents do not matter."""
+    a, b, P = _fid_cov_check(a, b)
+    return _fid_call(a, b, P, events, workspace, FID_COV_EVENTS, "dt_fid_cov_workspace_bytes", "dt_fid_cov_distance")
+
+
+def fid_route(n_a, n_b, D):
+    """"samples" (``device_fid``: the smaller set has at most 2048 rows; every shape that route took before keeps it, and
+    its bits) or "features" (``device_fid_cov``: both sets are longer than that and D <= 2048); ValueError if neither."""
+    if min(n_a, n_b) <= FID_MAX_SIDE:
+        return "samples"
+    if D <= FID_COV_MAX_WIDTH:
+        return "features"
+    raise ValueError(f"n_a={n_a}, n_b={n_b}, D={D}: the device Fréchet distance takes min(n_a, n_b) <= {FID_MAX_SIDE} "
+                     f"(the sample-space route) or a feature width D <= {FID_COV_MAX_WIDTH} (the feature-space route)")
+
+
+def device_fid_auto(a, b, events=None, workspace=None):
+    """``device_fid`` or ``device_fid_cov``, whichever ``fid_route`` names for the shapes of a and b (``events`` and
+    ``workspace`` are that route's)."""
+    a, b, _ = _set_pair(a, b)
+    route = fid_route(a.shape[-2], b.shape[-2], a.shape[-1])
+    return (device_fid if route == "samples" else device_fid_cov)(a, b, events=events, workspace=workspace)
 
 
 # ---------------------------------------------------------------------- KID, precision / recall, density / coverage

@@ -20,6 +20,7 @@
  * (rounding) clamped to 0.  No D x D matrix is formed.  Every sum has a fixed order: a problem's outputs do not depend on
  * P, on its neighbours or on the strides.  The result is not clamped: two equal sets give a value within rounding of 0
  * that may be negative.  A set without variance is no error: its trace and the cross term are 0.
+ * Sets of more than 2048 rows each go through include/dt_hip_fid_cov.h (the same outputs by the feature-space formula).
  */
 #ifndef DT_HIP_FID_H
 #define DT_HIP_FID_H
