@@ -150,6 +150,14 @@ QUALITY_SIGNATURES = {
                                   c_void_p, c_size_t, c_void_p, c_void_p]),
 }
 
+# name -> (restype, argtypes) of every symbol include/dt_hip_quality_stream.h declares (the same scores by row panels)
+QUALITY_STREAM_SIGNATURES = {
+    "dt_quality_stream_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "dt_quality_stream_scores": (c_int, [c_void_p, c_int, c_longlong, c_longlong, c_void_p, c_int, c_longlong, c_longlong,
+                                         c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_size_t, c_void_p, c_void_p]),
+}
+
 # name -> (restype, argtypes) of every symbol include/dt_hip_edit.h declares (the editing stage: masked loops, hole statistics)
 EDIT_SIGNATURES = {
     "dt_edit_start": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
@@ -189,7 +197,8 @@ def load(path=None):
     except OSError as e:
         raise HipLibraryError(f"cannot load {path}: {e}. There is no CPU fallback.") from e
     for name, (res, args) in {**SIGNATURES, **NOISE_SIGNATURES, **INCEPTION_SIGNATURES, **PCA_SIGNATURES,
-                              **FID_SIGNATURES, **FID_COV_SIGNATURES, **LPIPS_SIGNATURES, **TSNE_SIGNATURES, **QUALITY_SIGNATURES, **EDIT_SIGNATURES}.items():
+                              **FID_SIGNATURES, **FID_COV_SIGNATURES, **LPIPS_SIGNATURES, **TSNE_SIGNATURES, **QUALITY_SIGNATURES,
+                              **QUALITY_STREAM_SIGNATURES, **EDIT_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

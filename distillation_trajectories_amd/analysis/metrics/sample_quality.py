@@ -1,7 +1,10 @@
 """Set-level sample quality beside FID, on the device: KID (the unbiased MMD^2 with the cubic polynomial kernel), improved
 precision / recall (Kynkäänniemi et al. 2019) and density / coverage (Naeem et al. 2020) of a teacher's and a student's
 Inception features (``engine.device_quality``, include/dt_hip_quality.h, which holds the definitions).  The first set is
-always the "real" one (the teacher), the second the "generated" one (a student).
+always the "real" one (the teacher), the second the "generated" one (a student).  Sets of up to 2048 rows go through whole
+Gram matrices, longer ones (up to 131072 rows each, k <= 1023) through row panels (``engine.device_quality_stream``,
+include/dt_hip_quality_stream.h); ``engine.device_quality_auto`` chooses, and FID beside them goes through
+``engine.device_fid_auto``.
 
 FID is strongly biased at the sample counts used here (50 by default, 64 - 512 in the grids); KID is not.  FID also folds
 fidelity and diversity into one number, which guidance scale and student size trade against each other; precision and
@@ -50,9 +53,10 @@ def calculate_kid_device(features_1, features_2, num_subsets=0, subset_size=None
     """KID between two feature sets [N, D] (fp32, on the device already, or host tensors / arrays that are uploaded
     first), in fp64 on the device: {"kid": the full-set unbiased estimate, "kid_mean", "kid_std": mean and population
     standard deviation over ``num_subsets`` subsets of ``subset_size`` rows (``kid_subset_tables`` with ``seed``; default
-    size min(N1, N2)), NaN when ``num_subsets`` is 0}, Python floats."""
+    size min(N1, N2)), NaN when ``num_subsets`` is 0}, Python floats.  Up to 131072 rows per set; with more than 2048 rows in
+    a set a subset takes at most 2048 rows (the usual protocol is 100 subsets of 1000), so ``subset_size`` must be given."""
     a, b = _on_device(features_1, features_2)
-    r = engine.device_quality(a, b, k=1, subsets=_subsets(len(a), len(b), num_subsets, subset_size, seed))
+    r = engine.device_quality_auto(a, b, k=1, subsets=_subsets(len(a), len(b), num_subsets, subset_size, seed))
     sub = r["kid_subsets"][0].cpu().numpy()
     return {"kid": float(r["kid"][0]), "kid_mean": float(sub.mean()) if len(sub) else float("nan"),
             "kid_std": float(sub.std()) if len(sub) else float("nan")}
@@ -60,9 +64,10 @@ def calculate_kid_device(features_1, features_2, num_subsets=0, subset_size=None
 
 def calculate_prdc_device(features_1, features_2, k=5):
     """{"precision", "recall", "density", "coverage"} (Python floats) of the generated set features_2 against the real
-    set features_1, with the k-th nearest-neighbour radii of ``prdc`` (self included, strict ``<``)."""
+    set features_1, with the k-th nearest-neighbour radii of ``prdc`` (self included, strict ``<``).  Up to 131072 rows per
+    set; k <= 1023 when a set has more than 2048 rows."""
     a, b = _on_device(features_1, features_2)
-    r = engine.device_quality(a, b, k=k)
+    r = engine.device_quality_auto(a, b, k=k)
     return {name: float(r[name][0]) for name in ("precision", "recall", "density", "coverage")}
 
 
@@ -73,10 +78,12 @@ def quality_sweep(teacher_model, student_models, config, num_samples, weights=No
                   num_subsets=0, subset_size=None, seed=0):
     """FID, KID, precision / recall and density / coverage of every student against one teacher.  Samples and features
     are made exactly as ``fid_sweep`` makes them (same sampler, same consumption of the CPU generator: its ``fid`` comes
-    out bit for bit under the same seed); then one batched ``engine.device_fid`` and one batched ``engine.device_quality``
-    with the teacher's features shared.  Returns numpy arrays per student: ``fid``, ``kid`` [n], ``kid_subsets``
-    [n, num_subsets], ``precision``, ``recall``, ``density``, ``coverage`` [n], ``counts`` [n, 4], ``status`` [n] (that of
-    the quality call; 1: a non-finite feature)."""
+    out bit for bit under the same seed); then one batched ``engine.device_fid_auto`` and one batched
+    ``engine.device_quality_auto`` with the teacher's features shared (up to 2048 samples: the calls ``engine.device_fid`` and
+    ``engine.device_quality`` as before; up to 131072: the feature-space and row-panel routes, subsets of at most 2048
+    rows).  Returns numpy arrays per student: ``fid``, ``kid`` [n], ``kid_subsets`` [n, num_subsets], ``precision``,
+    ``recall``, ``density``, ``coverage`` [n], ``counts`` [n, 4], ``status`` [n] (that of the quality call; 1: a non-finite
+    feature)."""
     student_models = list(student_models)
     if not student_models:
         raise ValueError("quality_sweep needs at least one student model")
@@ -93,8 +100,8 @@ def quality_sweep(teacher_model, student_models, config, num_samples, weights=No
     teacher = features(teacher_model)
     students = torch.stack([features(m) for m in student_models])
     n_a, n_b = teacher.shape[0], students.shape[1]
-    fid = engine.device_fid(teacher, students)
-    res = engine.device_quality(teacher, students, k=k, subsets=_subsets(n_a, n_b, num_subsets, subset_size, seed))
+    fid = engine.device_fid_auto(teacher, students)
+    res = engine.device_quality_auto(teacher, students, k=k, subsets=_subsets(n_a, n_b, num_subsets, subset_size, seed))
     out = {name: res[name].cpu().numpy() for name in _SCORES}
     out["fid"] = fid["fid"].cpu().numpy()
     return out
@@ -104,9 +111,9 @@ def guidance_quality_sweep(teacher_model, student_models, config, guidance_scale
                            num_subsets=0, subset_size=None, seed=0):
     """The same scores per guidance scale: ``sample_grid`` for each model exactly as ``lpips_sweep`` and ``pca_sweep`` run
     it (sample s starts from seed 42 + s, one noise table), Inception features of the final states with the map
-    (0.5, 0.5), and per scale one batched ``engine.device_fid`` and ``engine.device_quality`` of every student against
-    the teacher at that scale.  Returns numpy arrays [n_students][n_scales] (``kid_subsets`` [..., num_subsets],
-    ``counts`` [..., 4])."""
+    (0.5, 0.5), and per scale one batched ``engine.device_fid_auto`` and ``engine.device_quality_auto`` of every student
+    against the teacher at that scale (the limits of ``quality_sweep``).  Returns numpy arrays [n_students][n_scales]
+    (``kid_subsets`` [..., num_subsets], ``counts`` [..., 4])."""
     from ..trajectory_engine import sample_grid
     from ...synthetic import noise_table
     C, H, T, S = config.channels, config.image_size, config.timesteps, num_samples
@@ -131,8 +138,8 @@ def guidance_quality_sweep(teacher_model, student_models, config, guidance_scale
         for gs in scales:
             teacher = features(t_grid, gs)
             batch = torch.stack([features(grid, gs) for grid in s_grids])
-            res = engine.device_quality(teacher, batch, k=k, subsets=subsets)
+            res = engine.device_quality_auto(teacher, batch, k=k, subsets=subsets)
             col = {name: res[name] for name in _SCORES}
-            col["fid"] = engine.device_fid(teacher, batch)["fid"]
+            col["fid"] = engine.device_fid_auto(teacher, batch)["fid"]
             cols.append(col)
         return {name: torch.stack([col[name] for col in cols], dim=1).cpu().numpy() for name in cols[0]}

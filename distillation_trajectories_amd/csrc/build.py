@@ -12,8 +12,8 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["dt_conv.hip", "dt_conv_bf16.hip", "dt_conv_strip.hip", "dt_layers.hip", "dt_update.hip", "dt_metrics.hip", "dt_fused.hip", "dt_unet.hip",
-           "dt_featnet.hip", "dt_inception.hip", "dt_pca.hip", "dt_fid.hip", "dt_lpips.hip", "dt_tsne.hip", "dt_quality.hip", "dt_edit.hip"]
-HEADERS = ["dt_internal.h", "dt_conv_forms.h", "dt_dense64.h", "dt_featnet.h", "dt_conv_epilogue.h", "dt_conv_walk.h", "dt_update_math.h", "dt_fused.h", os.path.join("..", "..", "include", "dt_hip.h"),
+           "dt_featnet.hip", "dt_inception.hip", "dt_pca.hip", "dt_fid.hip", "dt_lpips.hip", "dt_tsne.hip", "dt_quality.hip", "dt_quality_stream.hip", "dt_edit.hip"]
+HEADERS = ["dt_internal.h", "dt_conv_forms.h", "dt_dense64.h", "dt_quality_math.h", "dt_featnet.h", "dt_conv_epilogue.h", "dt_conv_walk.h", "dt_update_math.h", "dt_fused.h", os.path.join("..", "..", "include", "dt_hip.h"),
            os.path.join("..", "..", "include", "dt_hip_noise.h"),
            os.path.join("..", "..", "include", "dt_hip_inception.h"),
            os.path.join("..", "..", "include", "dt_hip_pca.h"),
@@ -22,6 +22,7 @@ HEADERS = ["dt_internal.h", "dt_conv_forms.h", "dt_dense64.h", "dt_featnet.h", "
            os.path.join("..", "..", "include", "dt_hip_lpips.h"),
            os.path.join("..", "..", "include", "dt_hip_tsne.h"),
            os.path.join("..", "..", "include", "dt_hip_quality.h"),
+           os.path.join("..", "..", "include", "dt_hip_quality_stream.h"),
            os.path.join("..", "..", "include", "dt_hip_edit.h")]
 LIB = os.path.join(HERE, "libdt_hip.so")
 ARCH = "gfx950"

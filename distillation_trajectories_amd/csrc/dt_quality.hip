@@ -18,11 +18,9 @@
 
 #include "../../include/dt_hip_quality.h"
 #include "dt_internal.h"
-#include "dt_dense64.h"
+#include "dt_quality_math.h"
 
 namespace {
-
-constexpr int kWave = 64;
 
 // per-problem workspace (doubles), after a head of P ints (the non-finite flag) rounded to 256 bytes
 struct Layout {
@@ -42,38 +40,6 @@ struct Layout {
   }
   __host__ __device__ size_t bytes(int P) const { return head + (size_t)P * per * sizeof(double); }
 };
-
-// Loader for tile_product: columns k .. k+3 of an fp32 row (nullptr: no such row) of len % 4 == 0 columns, as they are
-struct PlainRow {
-  const float *row;
-  int len;
-  static constexpr int W = 4;
-  __device__ void operator()(int k, double (&v)[4]) const {
-    v[0] = v[1] = v[2] = v[3] = 0.0;
-    if (row && k < len) {
-      const float4 x = *reinterpret_cast<const float4 *>(row + k);
-      v[0] = (double)x.x; v[1] = (double)x.y; v[2] = (double)x.z; v[3] = (double)x.w;
-    }
-  }
-};
-
-// squared distance from the three Gram entries; 0 exactly where all three have the same bits
-__device__ inline double dist2(double gxx, double gyy, double gxy) { return fmax(0.0, (gxx + gyy) - 2.0 * gxy); }
-
-__device__ inline double kappa(double g, double d) {
-  const double t = g / d + 1.0;
-  return t * t * t;
-}
-
-__device__ inline int wave_sum_int(int s) {
-  for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
-  return s;
-}
-
-__device__ inline double kid_value(double saa, double sbb, double sab, int n_a, int n_b) {
-  const double na = (double)n_a, nb = (double)n_b;
-  return saa / (na * (na - 1.0)) + sbb / (nb * (nb - 1.0)) - 2.0 * sab / (na * nb);
-}
 
 // ---------------------------------------------------------------------------------------------- 1. Gram matrices
 // blockIdx.x: the upper-triangle tiles of G_AA, then those of G_BB, then all tiles of G_AB
@@ -257,20 +223,6 @@ __global__ __launch_bounds__(kThreads) void quality_subset_kernel(int n_a, int n
     for (int c = 0; c < 3; ++c) tot[c] = (part[c][0] + part[c][1]) + (part[c][2] + part[c][3]);
     *out = kid_value(tot[0], tot[1], tot[2], m, m);
   }
-}
-
-// fixed-tree sum of 64-bit integers over the block; every thread gets the result
-__device__ long long block_sum_int(long long s, long long *red) {
-  const int t = threadIdx.x;
-  red[t] = s;
-  __syncthreads();
-  for (int h = kThreads / 2; h >= 1; h >>= 1) {
-    if (t < h) red[t] += red[t + h];
-    __syncthreads();
-  }
-  const long long r = red[0];
-  __syncthreads();
-  return r;
 }
 
 __global__ __launch_bounds__(kThreads) void quality_finish_kernel(int n_a, int n_b, int S, const double *ws, size_t per,

@@ -1219,6 +1219,141 @@ def device_quality(a, b, k=5, subsets=None, radii=False, events=None, workspace=
     return out
 
 
+# ---------------------------------------------------------------------- the same scores by row panels
+# (include/dt_hip_quality_stream.h)
+QUALITY_STREAM_MAX_ROWS = 131072
+QUALITY_STREAM_MAX_K = 1023
+QUALITY_STREAM_EVENTS = 6
+QUALITY_STREAM_PANEL_ROWS = 1024          # the default panel, before it is cut to the rows and the workspace cap
+QUALITY_STREAM_WORKSPACE_CAP = 2 << 30    # the default panel is lowered while the workspace would exceed this
+QUALITY_SUBSET_CHUNK = 16                 # subsets per device_quality call of the panel route's subset KIDs
+
+
+def _quality_stream_check(a, b, k, panel_rows):
+    a, b, P = _set_pair(a, b)
+    for t, name in ((a, "a"), (b, "b")):
+        if not 2 <= t.shape[-2] <= QUALITY_STREAM_MAX_ROWS:
+            raise ValueError(f"{name} holds {t.shape[-2]} rows: the row-panel route of the device sample-quality scores "
+                             f"takes 2 .. {QUALITY_STREAM_MAX_ROWS} per set")
+    _batch_limits(P, a.shape[-1])
+    k_max = min(a.shape[-2], b.shape[-2]) - 1
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= min(k_max, QUALITY_STREAM_MAX_K):
+        raise ValueError(f"k={k!r} must be an integer in [1, min(n_a, n_b) - 1] = [1, {k_max}] and at most "
+                         f"{QUALITY_STREAM_MAX_K} on the row-panel route")
+    if panel_rows is not None and (isinstance(panel_rows, bool) or not isinstance(panel_rows, (int, np.integer)) or
+                                   not 64 <= panel_rows <= 4096 or panel_rows % 64):
+        raise ValueError(f"panel_rows={panel_rows!r} must be None or a multiple of 64 in [64, 4096]")
+    return a, b, P
+
+
+def quality_stream_panel_rows(lib, P, n_a, n_b, D):
+    """the default panel of ``device_quality_stream``: 1024 rows, cut to the rows there are (rounded up to 64), lowered in
+    steps of 64 while ``dt_quality_stream_workspace_bytes`` exceeds 2 GiB"""
+    rows = min(QUALITY_STREAM_PANEL_ROWS, (max(n_a, n_b) + 63) // 64 * 64)
+    while rows > 64 and lib.dt_quality_stream_workspace_bytes(P, n_a, n_b, D, rows) > QUALITY_STREAM_WORKSPACE_CAP:
+        rows -= 64
+    return rows
+
+
+def device_quality_stream(a, b, k=5, radii=False, panel_rows=None, events=None, workspace=None):
+    """``device_quality`` by the row-panel route (dt_quality_stream_scores, whose header holds the method and the
+    contract): the same input forms, the same definitions and the same returned dict (``kid_subsets`` is [P, 0]: this
+    entry takes no subset tables), for sets of 2 .. 131072 rows each and k <= 1023.  No n x n matrix is held: the
+    workspace is one panel of ``panel_rows`` rows of a Gram matrix per problem.  ``panel_rows``: None (1024, cut to the
+    rows there are and lowered in steps of 64 while the workspace would exceed 2 GiB) or a multiple of 64 in 64 .. 4096;
+    the outputs do not depend on it.  With a 2-D ``a`` next to a 3-D ``b`` the teacher's side is formed once.  Where both
+    routes apply they agree to rounding (radii, KID), not to the bit.  ``events``: None or 6
+    torch.cuda.Event(enable_timing=True) (start, diagonals and flags, the A side, the B side, the A x B panels, end).
+    ``workspace``: None or a uint8 device tensor of at least ``dt_quality_stream_workspace_bytes`` bytes; its contents do
+    not matter."""
+    a, b, P = _quality_stream_check(a, b, k, panel_rows)
+    n_a, n_b, D = a.shape[-2], b.shape[-2], a.shape[-1]
+    if events is not None and len(events) != QUALITY_STREAM_EVENTS:
+        raise ValueError(f"events must be {QUALITY_STREAM_EVENTS} torch.cuda.Event")
+    _require_cuda(a, "a")
+    _require_cuda(b, "b")
+    if a.device != b.device:
+        raise ValueError(f"a is on {a.device}, b on {b.device}")
+    lib = _hip.load()
+    (a, a_ps, a_rs), (b, b_ps, b_rs) = _fid_rows(a), _fid_rows(b)
+    dev = a.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    kid = torch.empty(P, **f64)
+    counts = torch.empty(P, 4, dtype=torch.int64, device=dev)
+    status = torch.empty(P, dtype=torch.int32, device=dev)
+    r2 = torch.empty(P, n_a + n_b, **f64) if radii else None
+    rows = int(panel_rows) if panel_rows is not None else quality_stream_panel_rows(lib, P, n_a, n_b, D)
+    ws_bytes = lib.dt_quality_stream_workspace_bytes(P, n_a, n_b, D, rows)
+    if ws_bytes == 0:
+        raise ValueError(f"dt_quality_stream_workspace_bytes rejects P={P}, n_a={n_a}, n_b={n_b}, D={D}, "
+                         f"panel_rows={rows}")
+    with torch.cuda.device(dev):
+        ev = _stage_events(events)
+        ws = workspace
+        if ws is None:
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        elif ws.dtype != torch.uint8 or ws.device != dev or not ws.is_contiguous() or ws.numel() < ws_bytes:
+            raise ValueError(f"workspace must be a contiguous uint8 tensor of >= {ws_bytes} bytes on {dev}")
+        check(lib.dt_quality_stream_scores(ptr(a), n_a, a_ps, a_rs, ptr(b), n_b, b_ps, b_rs, P, D, int(k), rows, ptr(kid),
+                                           ptr(counts), ptr(r2), ptr(status), ptr(ws), ws_bytes, ev, stream_ptr()),
+              "dt_quality_stream_scores")
+        c = counts.to(torch.float64)
+        bad = counts[:, 0] < 0
+        out = {"kid": kid, "kid_subsets": torch.empty(P, 0, **f64), "counts": counts, "status": status}
+        for name, col, den in (("precision", 0, n_b), ("recall", 1, n_a), ("density", 2, int(k) * n_b),
+                               ("coverage", 3, n_a)):
+            # a tensor divisor, as in device_quality
+            out[name] = torch.where(bad, torch.full_like(c[:, col], float("nan")),
+                                    c[:, col] / torch.full_like(c[:, col], float(den)))
+        if radii:
+            out["radii_a"], out["radii_b"] = r2[:, :n_a], r2[:, n_a:]
+    return out
+
+
+def quality_route(n_a, n_b, k):
+    """"matrices" (``device_quality``: both sets have at most 2048 rows; every shape that route took before keeps it, and
+    its bits) or "panels" (``device_quality_stream``: up to 131072 rows per set, k <= 1023); ValueError if neither."""
+    if max(n_a, n_b) <= QUALITY_MAX_ROWS:
+        return "matrices"
+    if max(n_a, n_b) > QUALITY_STREAM_MAX_ROWS:
+        raise ValueError(f"n_a={n_a}, n_b={n_b}: the device sample-quality scores take at most {QUALITY_MAX_ROWS} rows per "
+                         f"set (whole Gram matrices) or at most {QUALITY_STREAM_MAX_ROWS} (row panels)")
+    if k > QUALITY_STREAM_MAX_K:
+        raise ValueError(f"k={k}: with more than {QUALITY_MAX_ROWS} rows in a set the device sample-quality scores go by "
+                         f"row panels, which take k <= {QUALITY_STREAM_MAX_K}")
+    return "panels"
+
+
+def device_quality_auto(a, b, k=5, subsets=None, radii=False):
+    """``device_quality`` or ``device_quality_stream``, whichever ``quality_route`` names for the shapes of a and b.  On
+    the panel route ``subsets=(idx_a, idx_b)`` is served by gathering each subset's rows on the device into [S', m, D]
+    tensors that go through ``device_quality(..., k=1)`` as problems of their own, at most 16 subsets per call; m <= 2048
+    there."""
+    a, b, P = _set_pair(a, b)
+    n_a, n_b = a.shape[-2], b.shape[-2]
+    if quality_route(n_a, n_b, k) == "matrices":
+        return device_quality(a, b, k=k, subsets=subsets, radii=radii)
+    if subsets is None:
+        return device_quality_stream(a, b, k=k, radii=radii)
+    ia, ib = _quality_subsets(subsets, n_a, n_b)
+    if ia.shape[1] > QUALITY_MAX_ROWS:
+        raise ValueError(f"subsets of size {ia.shape[1]}: with more than {QUALITY_MAX_ROWS} rows in a set a subset's KID is "
+                         f"computed on its gathered rows, which takes subsets of at most {QUALITY_MAX_ROWS} rows")
+    out = device_quality_stream(a, b, k=k, radii=radii)
+    dev = out["kid"].device
+    ia, ib = (torch.from_numpy(t).to(dev).long() for t in (ia, ib))
+    cols = []
+    for s0 in range(0, ia.shape[0], QUALITY_SUBSET_CHUNK):
+        ca, cb = ia[s0:s0 + QUALITY_SUBSET_CHUNK], ib[s0:s0 + QUALITY_SUBSET_CHUNK]
+        per_problem = []
+        for p in range(P):
+            rows_a, rows_b = (a[p] if a.dim() == 3 else a), (b[p] if b.dim() == 3 else b)
+            per_problem.append(device_quality(rows_a[ca], rows_b[cb], k=1)["kid"])
+        cols.append(torch.stack(per_problem))
+    out["kid_subsets"] = torch.cat(cols, dim=1)
+    return out
+
+
 # ---------------------------------------------------------------------- perceptual distance (include/dt_hip_lpips.h)
 def device_lpips(handle, images0, images1, in_scale=1.0, in_shift=0.0, per_layer=False):
     """LPIPS (v0.1, net='alex') between images0 [n0, 3, H, W] (n0 = 1: one image against all) and images1 [n1, 3, H, W]
