@@ -173,6 +173,17 @@ EDIT_SIGNATURES = {
                                      c_void_p, c_void_p]),
 }
 
+# name -> (restype, argtypes) of every symbol include/dt_hip_rng.h declares (sampler noise: the torch CPU generator's stream)
+RNG_SIGNATURES = {
+    "dt_rng_mt19937_words": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_longlong, c_longlong, c_void_p, c_longlong, c_void_p,
+                                     c_void_p, c_void_p]),
+    "dt_rng_normal_from_words": (c_int, [c_void_p, c_longlong, c_int, c_longlong, c_longlong, c_int, c_void_p, c_longlong,
+                                         c_longlong, c_longlong, c_void_p]),
+    "dt_rng_workspace_bytes": (c_size_t, [c_int, c_longlong, c_int]),
+    "dt_rng_randn": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_longlong, c_longlong, c_longlong, c_int, c_void_p,
+                             c_longlong, c_longlong, c_longlong, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+}
+
 
 class TsneParams(ctypes.Structure):
     """dt_tsne_params of include/dt_hip_tsne.h"""
@@ -198,7 +209,7 @@ def load(path=None):
         raise HipLibraryError(f"cannot load {path}: {e}. There is no CPU fallback.") from e
     for name, (res, args) in {**SIGNATURES, **NOISE_SIGNATURES, **INCEPTION_SIGNATURES, **PCA_SIGNATURES,
                               **FID_SIGNATURES, **FID_COV_SIGNATURES, **LPIPS_SIGNATURES, **TSNE_SIGNATURES, **QUALITY_SIGNATURES,
-                              **QUALITY_STREAM_SIGNATURES, **EDIT_SIGNATURES}.items():
+                              **QUALITY_STREAM_SIGNATURES, **EDIT_SIGNATURES, **RNG_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -87,6 +87,11 @@ def posterior_coefficients(config):
     return rows
 
 
+def noise_kw(noise):
+    """The ``noise`` keyword for a callee only when the caller was given one, so that a call without it is the call it was."""
+    return {} if noise is None else {"noise": noise}
+
+
 def _run(model, x0, config, z):
     """Final samples [S,C,H,W] (device) for start images x0[S,C,H,W] and step noise z[T-1,S,E]."""
     h = engine.UNetHandle.for_module(model)
@@ -102,26 +107,46 @@ def _run(model, x0, config, z):
     return traj[T].reshape(S, C, H, W).clone()
 
 
-def p_sample_loop(model, x, config):
-    """Reference :261-318: denoise ``x`` through all config.timesteps steps; returns the final sample."""
+def p_sample_loop(model, x, config, noise=None):
+    """Reference :261-318: denoise ``x`` through all config.timesteps steps; returns the final sample.  ``noise``: "host" (the
+    default, unless ``$DT_NOISE`` says otherwise) draws the step noise on the CPU generator, "device" makes the same draws on
+    the device and leaves the generator where the host draws would have (``engine.noise_mode``)."""
     model.eval()
     T = config.timesteps
+    if engine.noise_mode(noise) == "device":
+        z = None
+        if T > 1:           # one stream continued from the host generator: T - 1 draws of x.numel() elements
+            z = torch.empty(T - 1, x.shape[0], x[0].numel(), dtype=torch.float32, device=next(model.parameters()).device)
+            engine.device_randn(state=engine.HostGenerator(), draws=T - 1, E=x.numel(), out=z, device=z.device)
+        return _run(model, x.detach().float(), config, z)
     zs = [torch.randn(x.shape) for _ in range(T - 1)]            # one CPU-generator draw per step with t > 0
     z = torch.stack(zs).reshape(T - 1, x.shape[0], -1) if zs else None
     return _run(model, x.detach().float(), config, z)
 
 
-def generate_samples(model, config, num_samples, device, fixed_samples=None):
-    """Reference :199-259: ``num_samples`` final samples [N,C,H,W]; all of them advance in one batched loop."""
+def generate_samples(model, config, num_samples, device, fixed_samples=None, noise=None):
+    """Reference :199-259: ``num_samples`` final samples [N,C,H,W]; all of them advance in one batched loop.  ``noise`` as for
+    ``p_sample_loop``: with "device" the start and step draws of all samples are one stream continued from the host
+    generator's state, written straight into the step-major buffers the sampler reads."""
     model.eval()
     image_size = getattr(model, "image_size", config.image_size)
     T = config.timesteps
+    device_noise = engine.noise_mode(noise) == "device"
     starts, zs = [], []
     if fixed_samples is not None:
         print(f"    Using {min(num_samples, len(fixed_samples))} fixed samples as starting points")
         n = len(fixed_samples[:num_samples])
     else:
         n = num_samples
+    if device_noise and fixed_samples is None:
+        # the reference's draw order is sample-major (start of sample i, then its T - 1 steps): draw i * T + k goes to row
+        # i of step k, so buf[0] holds the starts and buf[1:] the step noise
+        E = config.channels * image_size * image_size
+        buf = torch.empty(T, n, E, dtype=torch.float32, device=next(model.parameters()).device)
+        if n:
+            engine.device_randn(state=engine.HostGenerator(), draws=(n, T), E=E, out=buf, strides=(0, E, n * E),
+                                device=buf.device)
+        return _run(model, buf[0].reshape(n, config.channels, image_size, image_size), config, buf[1:] if T > 1 else None)
     for i in range(n):           # reference draw order: start noise of sample i, then its T-1 step draws
         if fixed_samples is not None:
             x = fixed_samples[i:i + 1].clone().cpu().float()
@@ -130,8 +155,17 @@ def generate_samples(model, config, num_samples, device, fixed_samples=None):
         else:
             x = torch.randn(1, config.channels, image_size, image_size)
         starts.append(x)
-        zs.append(torch.stack([torch.randn(x.shape) for _ in range(T - 1)]) if T > 1 else None)
+        if not device_noise:
+            zs.append(torch.stack([torch.randn(x.shape) for _ in range(T - 1)]) if T > 1 else None)
     x0 = torch.cat(starts)
+    if device_noise:             # fixed starting points: only the T - 1 step draws per sample
+        z = None
+        if T > 1:
+            E = x0[0].numel()
+            z = torch.empty(T - 1, n, E, dtype=torch.float32, device=next(model.parameters()).device)
+            engine.device_randn(state=engine.HostGenerator(), draws=(n, T - 1), E=E, out=z, strides=(0, E, n * E),
+                                device=z.device)
+        return _run(model, x0, config, z)
     z = torch.stack(zs, dim=1).reshape(T - 1, n, -1) if T > 1 else None
     return _run(model, x0, config, z)
 
@@ -167,10 +201,10 @@ def extract_features(images, model=None, weights=None, device=None, batch_size=6
 
 
 def calculate_and_visualize_fid(teacher_model, student_model, config, output_dir=None, size_factor=None,
-                                fixed_samples=None, weights=None, stats=None):
+                                fixed_samples=None, weights=None, stats=None, noise=None):
     """Reference :96-198: FID between teacher and student samples; console lines, ``fid_score_size_{sf}.txt`` and the
     returned ``{"fid_score": ...}`` as the reference's.  No figure is drawn.  ``stats``: "host" (the default, unless
-    ``$DT_FID_STATS`` says otherwise) or "device" (``stats_mode``)."""
+    ``$DT_FID_STATS`` says otherwise) or "device" (``stats_mode``); ``noise`` as for ``generate_samples``."""
     mode = stats_mode(stats)
     if output_dir is None:
         output_dir = os.path.join(config.analysis_dir, "fid", f"size_{size_factor}")
@@ -181,9 +215,9 @@ def calculate_and_visualize_fid(teacher_model, student_model, config, output_dir
     student_model.eval()
     num_samples = config.num_samples if hasattr(config, 'num_samples') else 50
     print("  Generating samples from teacher model...")
-    teacher_samples = generate_samples(teacher_model, config, num_samples, device, fixed_samples=fixed_samples)
+    teacher_samples = generate_samples(teacher_model, config, num_samples, device, fixed_samples=fixed_samples, **noise_kw(noise))
     print("  Generating samples from student model...")
-    student_samples = generate_samples(student_model, config, num_samples, device, fixed_samples=fixed_samples)
+    student_samples = generate_samples(student_model, config, num_samples, device, fixed_samples=fixed_samples, **noise_kw(noise))
     print("  Extracting features using InceptionV3...")
     inception_model = InceptionModel(device, weights)
     if mode == "device":
@@ -200,12 +234,13 @@ def calculate_and_visualize_fid(teacher_model, student_model, config, output_dir
     return {"fid_score": fid_score}
 
 
-def fid_sweep(teacher_model, student_models, config, num_samples, weights=None, fixed_samples=None):
+def fid_sweep(teacher_model, student_models, config, num_samples, weights=None, fixed_samples=None, noise=None):
     """FID of every student against one teacher: the teacher's samples and features once, each student's samples and
     features (``generate_samples`` in that order, so the CPU generator is consumed as by one
     ``calculate_and_visualize_fid`` call for the teacher followed by the students), then one batched
     ``engine.device_fid_auto`` with the teacher's features shared.  Returns numpy ``fid [n_students]`` and
-    ``parts [n_students, 4]`` (float64) and ``status [n_students]``; nothing else leaves the device."""
+    ``parts [n_students, 4]`` (float64) and ``status [n_students]``; nothing else leaves the device.  ``noise`` as for
+    ``generate_samples``."""
     student_models = list(student_models)
     if not student_models:
         raise ValueError("fid_sweep needs at least one student model")
@@ -216,7 +251,7 @@ def fid_sweep(teacher_model, student_models, config, num_samples, weights=None, 
 
     def features(model):
         model.eval()
-        samples = generate_samples(model, config, num_samples, device, fixed_samples=fixed_samples)
+        samples = generate_samples(model, config, num_samples, device, fixed_samples=fixed_samples, **noise_kw(noise))
         return extract_features(samples, inception_model, batch_size=32, in_scale=0.5, in_shift=0.5)
 
     teacher = features(teacher_model)

@@ -75,7 +75,7 @@ _SCORES = ("kid", "kid_subsets", "precision", "recall", "density", "coverage", "
 
 
 def quality_sweep(teacher_model, student_models, config, num_samples, weights=None, fixed_samples=None, k=5,
-                  num_subsets=0, subset_size=None, seed=0):
+                  num_subsets=0, subset_size=None, seed=0, noise=None):
     """FID, KID, precision / recall and density / coverage of every student against one teacher.  Samples and features
     are made exactly as ``fid_sweep`` makes them (same sampler, same consumption of the CPU generator: its ``fid`` comes
     out bit for bit under the same seed); then one batched ``engine.device_fid_auto`` and one batched
@@ -83,7 +83,7 @@ def quality_sweep(teacher_model, student_models, config, num_samples, weights=No
     ``engine.device_quality`` as before; up to 131072: the feature-space and row-panel routes, subsets of at most 2048
     rows).  Returns numpy arrays per student: ``fid``, ``kid`` [n], ``kid_subsets`` [n, num_subsets], ``precision``,
     ``recall``, ``density``, ``coverage`` [n], ``counts`` [n, 4], ``status`` [n] (that of the quality call; 1: a non-finite
-    feature)."""
+    feature).  ``noise``: where the sampler's noise is drawn, as for ``fid_score.generate_samples``."""
     student_models = list(student_models)
     if not student_models:
         raise ValueError("quality_sweep needs at least one student model")
@@ -94,7 +94,8 @@ def quality_sweep(teacher_model, student_models, config, num_samples, weights=No
 
     def features(model):
         model.eval()
-        samples = fid_score.generate_samples(model, config, num_samples, device, fixed_samples=fixed_samples)
+        samples = fid_score.generate_samples(model, config, num_samples, device, fixed_samples=fixed_samples,
+                                             **fid_score.noise_kw(noise))
         return fid_score.extract_features(samples, inception_model, batch_size=32, in_scale=0.5, in_shift=0.5)
 
     teacher = features(teacher_model)
@@ -108,12 +109,13 @@ def quality_sweep(teacher_model, student_models, config, num_samples, weights=No
 
 
 def guidance_quality_sweep(teacher_model, student_models, config, guidance_scales, num_samples, weights=None, k=5,
-                           num_subsets=0, subset_size=None, seed=0):
+                           num_subsets=0, subset_size=None, seed=0, noise=None):
     """The same scores per guidance scale: ``sample_grid`` for each model exactly as ``lpips_sweep`` and ``pca_sweep`` run
     it (sample s starts from seed 42 + s, one noise table), Inception features of the final states with the map
     (0.5, 0.5), and per scale one batched ``engine.device_fid_auto`` and ``engine.device_quality_auto`` of every student
     against the teacher at that scale (the limits of ``quality_sweep``).  Returns numpy arrays [n_students][n_scales]
-    (``kid_subsets`` [..., num_subsets], ``counts`` [..., 4])."""
+    (``kid_subsets`` [..., num_subsets], ``counts`` [..., 4]).  ``noise``: where the noise table is made
+    (``synthetic.noise_table``)."""
     from ..trajectory_engine import sample_grid
     from ...synthetic import noise_table
     C, H, T, S = config.channels, config.image_size, config.timesteps, num_samples
@@ -131,7 +133,7 @@ def guidance_quality_sweep(teacher_model, student_models, config, guidance_scale
                                           in_scale=0.5, in_shift=0.5)
 
     with torch.cuda.device(device):
-        table = noise_table(42, S + T - 1, (1, C, H, H)).reshape(S + T - 1, -1).to(device)
+        table = noise_table(42, S + T - 1, (1, C, H, H), **fid_score.noise_kw(noise)).reshape(S + T - 1, -1).to(device)
         t_grid = sample_grid(engine.UNetHandle.for_module(teacher_model), table, 0, S, T, scales, H, H)
         s_grids = [sample_grid(engine.UNetHandle.for_module(m), table, 0, S, T, scales, H, H) for m in students]
         cols = []

@@ -668,6 +668,171 @@ def device_sample_mean(traj):
     return out
 
 
+# ---------------------------------------------------------------------- sampler noise on the device (include/dt_hip_rng.h)
+RNG_STATE_WORDS = 624           # DT_RNG_STATE_WORDS
+RNG_MIN_ELEMENTS = 16           # below it torch.randn takes a double-precision scalar path that the library does not provide
+
+
+def noise_mode(noise=None):
+    """"host" or "device": ``noise`` if given, else ``$DT_NOISE``, else "host".  "host" draws sampler noise with the torch
+    CPU generator and uploads it; "device" makes the same numbers on the device (``device_randn``)."""
+    mode = noise if noise is not None else (os.environ.get("DT_NOISE") or "host")
+    if mode not in ("host", "device"):
+        raise ValueError(f"noise (or DT_NOISE) must be 'host' or 'device', got {mode!r}")
+    return mode
+
+
+class HostGenerator:
+    """The global torch CPU generator as the library's (state words, position): ``words`` uint32 [624], ``pos`` in 0..624
+    (624: the block is used up, or the generator is fresh from ``manual_seed``), read from the 5056 bytes of
+    ``torch.get_rng_state()`` (seed 8 bytes, left int32, seeded 4 bytes, next 8 bytes, 624 words as uint64, then the
+    normal-sample cache).  ``write`` puts a walk's end back: seed, seeded flag and the cache stay as they were read."""
+    STATE_BYTES = 5056
+
+    def __init__(self, raw=None):
+        raw = torch.get_rng_state() if raw is None else raw
+        b = np.array(raw.numpy() if isinstance(raw, torch.Tensor) else raw, dtype=np.uint8)
+        if b.shape != (self.STATE_BYTES,):
+            raise ValueError(f"a torch CPU generator state has {self.STATE_BYTES} bytes, got {b.shape}")
+        self.raw = b
+        left, nxt = int(b[8:12].view(np.int32)[0]), int(b[16:24].view(np.uint64)[0])
+        self.words = b[24:24 + 8 * RNG_STATE_WORDS].view(np.uint64).astype(np.uint32)
+        self.pos = RNG_STATE_WORDS if left == 1 else nxt
+        if not 0 <= self.pos <= RNG_STATE_WORDS:
+            raise ValueError(f"generator state with next = {nxt}")
+
+    def state_bytes(self, words, pos):
+        """The 5056 bytes of this generator moved to (``words``, ``pos``): next = pos and left = 625 - pos, which is how the
+        generator leaves them once it has produced a word."""
+        words, pos = np.asarray(words).reshape(-1).view(np.uint32), int(pos)
+        if words.shape != (RNG_STATE_WORDS,) or not 0 <= pos <= RNG_STATE_WORDS:
+            raise ValueError("an mt19937 state is 624 words and a position in 0..624")
+        b = self.raw.copy()
+        b[8:12] = np.array([RNG_STATE_WORDS + 1 - pos], np.int32).view(np.uint8)
+        b[16:24] = np.array([pos], np.uint64).view(np.uint8)
+        b[24:24 + 8 * RNG_STATE_WORDS] = words.astype(np.uint64).view(np.uint8)
+        return b
+
+    def write(self, words, pos):
+        """``torch.set_rng_state`` of ``state_bytes(words, pos)``; ``words`` / ``pos`` may be the device tensors an entry
+        returned (one stream)."""
+        if isinstance(words, torch.Tensor):
+            words = words.detach().cpu().contiguous().numpy()
+        if isinstance(pos, torch.Tensor):
+            pos = int(pos.reshape(-1)[0])
+        torch.set_rng_state(torch.from_numpy(self.state_bytes(words, pos)))
+
+
+def _rng_start(seeds, state, device):
+    """(seeds, state words, positions) device tensors (None where unused), S and the device of a call's streams."""
+    if (seeds is None) == (state is None):
+        raise ValueError("give either seeds= or state=")
+    device = torch.device("cuda" if device is None else device)
+    if device.type != "cuda":
+        raise HipLibraryError(f"the device RNG runs on the GPU only, got device {device}")
+    if seeds is not None:
+        if isinstance(seeds, torch.Tensor):
+            vals = [int(v) for v in seeds.reshape(-1).tolist()]
+        else:
+            vals = [int(v) for v in (seeds if isinstance(seeds, (list, tuple, range, np.ndarray)) else [seeds])]
+        if not vals:
+            raise ValueError("seeds is empty")
+        # torch.manual_seed keys the mt19937 with the seed mod 2**32
+        return torch.tensor([v % 2 ** 32 for v in vals], dtype=torch.int64, device=device), None, None, len(vals), device
+    words, pos = (state.words, state.pos) if isinstance(state, HostGenerator) else state
+    if isinstance(words, torch.Tensor):
+        words = words.to(device).contiguous()
+        if words.dtype != torch.int32:
+            raise ValueError("state words as a tensor are int32 (the bits of the uint32 words)")
+    else:
+        words = torch.from_numpy(np.ascontiguousarray(words, dtype=np.uint32).view(np.int32)).to(device)
+    words = words.reshape(-1, RNG_STATE_WORDS)
+    S = words.shape[0]
+    if isinstance(pos, torch.Tensor):
+        pos = pos.to(device=device, dtype=torch.int32).reshape(-1).contiguous()
+    else:
+        plist = [int(v) for v in np.asarray(pos).reshape(-1)]
+        if any(not 0 <= v <= RNG_STATE_WORDS for v in plist):
+            raise ValueError("a position is in 0..624")
+        pos = torch.tensor(plist, dtype=torch.int32, device=device)
+    if pos.numel() != S:
+        raise ValueError(f"{S} states but {pos.numel()} positions")
+    return None, words, pos, S, device
+
+
+def device_mt19937_words(seeds=None, state=None, n=0, skip=0, out=None, device=None, return_state=False):
+    """int32 [S, n]: the bits of ``n`` tempered mt19937 words of each stream after skipping ``skip`` (dt_rng_mt19937_words).
+    Streams start from ``seeds`` (an int or a sequence; what ``torch.manual_seed`` would key) or from ``state``, a
+    ``HostGenerator`` or ``(words [S, 624], pos [S])``.  ``return_state``: also ``(words int32 [S, 624], pos int32 [S])`` on the
+    device where the walks end."""
+    lib = _hip.load()
+    seeds_t, st_t, pos_t, S, device = _rng_start(seeds, state, device)
+    n, skip = int(n), int(skip)
+    if out is None:
+        out = torch.empty(S, max(n, 0), dtype=torch.int32, device=device)
+    _require_cuda(out, "out")
+    if out.dtype != torch.int32 or not out.is_contiguous() or out.dim() != 2 or out.shape[0] != S or out.shape[1] < n:
+        raise ValueError(f"out must be a contiguous int32 [S, >= n] tensor, got {tuple(out.shape)} {out.dtype}")
+    end = (torch.empty(S, RNG_STATE_WORDS, dtype=torch.int32, device=device),
+           torch.empty(S, dtype=torch.int32, device=device)) if return_state else (None, None)
+    with torch.cuda.device(device):
+        check(lib.dt_rng_mt19937_words(ptr(seeds_t), ptr(st_t), ptr(pos_t), S, skip, n, ptr(out), out.shape[1], ptr(end[0]),
+                                       ptr(end[1]), stream_ptr()), "dt_rng_mt19937_words")
+    return (out, end) if return_state else out
+
+
+def device_randn(seeds=None, state=None, draws=1, E=None, out=None, strides=None, skip=0, device=None, return_state=False,
+                 workspace=None):
+    """The draws ``torch.randn(E)`` would give on the host, made on the device (dt_rng_randn), bit for bit.
+
+    Every stream (``seeds`` or ``state`` as for ``device_mt19937_words``) gives ``draws`` consecutive draws of ``E >= 16``
+    fp32 elements after skipping ``skip`` words.  ``draws`` is a count, or ``(A, B)``: draw ``a * B + b`` of stream ``s`` is
+    written at ``out.view(-1)[s * strides[0] + a * strides[1] + b * strides[2] :][:E]`` and nothing else of ``out`` is
+    touched; the default is a new ``[S, A * B, E]`` tensor.  With ``state`` a ``HostGenerator`` the global CPU generator
+    is afterwards where the same draws on the host would have left it.  ``return_state``: also the end ``(words, pos)``.
+    ``workspace``: a uint8 device tensor of any size from ``dt_rng_workspace_bytes(S, 1, E)`` up (default: the
+    library's bounded suggestion)."""
+    lib = _hip.load()
+    if E is None:
+        raise ValueError("E, the elements per draw, is required")
+    E, skip = int(E), int(skip)
+    if E < RNG_MIN_ELEMENTS:
+        raise HipLibraryError(f"device_randn draws at least {RNG_MIN_ELEMENTS} elements per draw, got E = {E}: below that "
+                              "torch.randn takes a double-precision scalar path that the library does not provide (DT_E_ARG)")
+    seeds_t, st_t, pos_t, S, device = _rng_start(seeds, state, device)
+    A, B = (int(draws[0]), int(draws[1])) if isinstance(draws, (tuple, list)) else (int(draws), 1)
+    n_draws = max(A, 0) * max(B, 0)
+    if out is None:
+        if strides is not None:
+            raise ValueError("strides need out")
+        out = torch.empty(S, n_draws, max(E, 0), dtype=torch.float32, device=device)
+        strides = (n_draws * E, B * E, E)
+    elif strides is None:
+        strides = (n_draws * E, B * E, E)
+    _require_cuda(out, "out")
+    ss, sa, sb = (int(v) for v in strides)
+    if out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 tensor")
+    if min(ss, sa, sb) < 0:
+        raise ValueError("strides are non-negative counts of floats")
+    if n_draws > 0 and E > 0 and (S - 1) * ss + (A - 1) * sa + (B - 1) * sb + E > out.numel():
+        raise ValueError(f"draws {(S, A, B)} of {E} elements with strides {(ss, sa, sb)} do not fit out ({out.numel()} floats)")
+    host = state if isinstance(state, HostGenerator) else None
+    want_state = return_state or (host is not None and n_draws > 0)
+    end = (torch.empty(S, RNG_STATE_WORDS, dtype=torch.int32, device=device),
+           torch.empty(S, dtype=torch.int32, device=device)) if want_state else (None, None)
+    if workspace is None:
+        need = lib.dt_rng_workspace_bytes(S, n_draws, E)
+        workspace = torch.empty(max(need, 4), dtype=torch.uint8, device=device)
+    _require_cuda(workspace, "workspace")
+    with torch.cuda.device(device):
+        check(lib.dt_rng_randn(ptr(seeds_t), ptr(st_t), ptr(pos_t), S, skip, A, B, E, ptr(out), ss, sa, sb, ptr(end[0]),
+                               ptr(end[1]), ptr(workspace), workspace.numel(), stream_ptr()), "dt_rng_randn")
+    if host is not None and n_draws > 0:
+        host.write(end[0][0], end[1][0])
+    return (out, end) if return_state else out
+
+
 # ---------------------------------------------------------------------- fp64 dense stages (csrc/dt_dense64.h)
 def _f32_rows(t, name, layouts):
     """t, a float32 torch tensor of 2 or 3 dims (``layouts`` names them in the error); shape errors are ValueErrors."""

@@ -61,7 +61,10 @@ def _side_streams(device, n):
 
 
 def _upload(host):
-    """Host tensor -> current device through pinned memory, asynchronously on the current stream."""
+    """Host tensor -> current device through pinned memory, asynchronously on the current stream; a tensor that is on a
+    device already (a noise table made there, ``$DT_NOISE=device``) only moves to the current one."""
+    if host.is_cuda:
+        return host.to(torch.device("cuda", torch.cuda.current_device()))
     return host.pin_memory().to(torch.device("cuda", torch.cuda.current_device()), non_blocking=True)
 
 

@@ -60,9 +60,23 @@ def seeded_noise(seed, shape):
     return torch.randn(*shape)
 
 
-def noise_table(first_seed, count, shape):
+def noise_table(first_seed, count, shape, noise=None, device=None):
     """[count, *shape] table N[k] = seeded_noise(first_seed + k): start noise of sample seed s is
-    N[s-first_seed]; step noise of (seed s, step t) is N[s+t-first_seed]."""
+    N[s-first_seed]; step noise of (seed s, step t) is N[s+t-first_seed].
+
+    ``noise="device"`` (or ``$DT_NOISE=device``; ``engine.noise_mode``) makes the same table on ``device`` (default: the
+    current GPU) instead, ``count`` independent streams of one draw each (``engine.device_randn``), and returns it there;
+    the default, "host", draws on the CPU generator and returns a CPU tensor.  Either way the global generator is left
+    as it was."""
+    from . import engine
+    if engine.noise_mode(noise) == "device":
+        E = 1
+        for v in shape:
+            E *= int(v)
+        out = torch.empty(count, *shape, dtype=torch.float32, device=torch.device("cuda" if device is None else device))
+        if count:
+            engine.device_randn(seeds=range(first_seed, first_seed + count), draws=1, E=E, out=out, device=out.device)
+        return out
     state = torch.get_rng_state()
     out = torch.stack([seeded_noise(first_seed + k, shape) for k in range(count)])
     torch.set_rng_state(state)

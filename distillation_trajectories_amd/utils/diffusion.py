@@ -102,12 +102,15 @@ def _p_sample_uniform(h, x, t_value, t_index, diffusion_params, guidance_scale, 
 
 @torch.no_grad()
 def p_sample_loop(model, shape, sample_steps, diffusion_params, device=None, config=None, track_trajectory=False,
-                  guidance_scale=1.0):
+                  guidance_scale=1.0, noise=None):
     """Whole reverse loop, device resident (reference utils/diffusion.py:160-212).
 
     Returns ``img`` (device tensor) or ``(img, trajectory)`` with the trajectory as a list of
     len(indices)+1 CPU tensors [B,C,H,W] (x_T first), exactly like the reference.  The caller is
     responsible for ``model.eval()`` as in the reference; the HIP path always uses running statistics.
+    ``noise``: "host" (the default, unless ``$DT_NOISE`` says otherwise) draws x_T and the step noise on the CPU generator
+    and uploads them; "device" makes the same draws on the device, one stream continued from the generator's state, and
+    leaves the generator where the host draws would have (``engine.noise_mode``).
     """
     if device is None:
         device = next(model.parameters()).device
@@ -119,12 +122,18 @@ def p_sample_loop(model, shape, sample_steps, diffusion_params, device=None, con
     indices = timestep_indices(sample_steps, num_timesteps)
     n = len(indices)
     # noise in the reference's draw order: x_T, then one z per step with index > 0
-    x_T = torch.randn(shape)
     has_noise = [i > 0 for i in indices]
-    z_host = [torch.randn(shape) for flag in has_noise if flag]
     traj = torch.empty(n + 1, B, E, dtype=torch.float32, device=device)
-    traj[0].copy_(x_T.reshape(B, E))
-    z = torch.stack(z_host).reshape(-1, E).to(device) if z_host else None
+    if engine.noise_mode(noise) == "device":
+        nz = sum(has_noise)
+        draws = engine.device_randn(state=engine.HostGenerator(), draws=1 + nz, E=B * E, device=device)[0]   # [1 + nz, B * E]
+        traj[0].copy_(draws[0].reshape(B, E))
+        z = draws[1:].reshape(-1, E) if nz else None
+    else:
+        x_T = torch.randn(shape)
+        z_host = [torch.randn(shape) for flag in has_noise if flag]
+        traj[0].copy_(x_T.reshape(B, E))
+        z = torch.stack(z_host).reshape(-1, E).to(device) if z_host else None
     z_shift, k = [], 0
     for flag in has_noise:
         z_shift.append(k * B)
