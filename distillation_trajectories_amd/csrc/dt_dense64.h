@@ -1,11 +1,12 @@
-// The fp64 dense core that dt_pca.hip (top-k eigenpairs of a centred Gram matrix) and dt_fid.hip (all eigenvalues of a
-// squared cross product) share: strided fp32 row sets, the column-quad mean, the staged 64 x 64 tile product with its
-// upper-triangle decode and mirrored store, Householder tridiagonalisation of a batch of symmetric matrices that live in
-// a caller's workspace, the bounds of the tridiagonal's spectrum and one eigenvalue of it by Sturm-count bisection.
-// Internal: included by those two translation units only, everything in an anonymous namespace.
+// The fp64 dense core that dt_pca.hip (top-k eigenpairs of a centred Gram matrix), dt_fid.hip (all eigenvalues of a
+// squared cross product), dt_tsne.hip and the two sample-quality routes (dt_quality.hip, dt_quality_stream.hip, through
+// dt_quality_math.h) share: strided fp32 row sets and what an entry point checks of them, the column-quad mean, the staged
+// 64 x 64 tile product on FMAs with its upper-triangle decode and mirrored store, Householder tridiagonalisation of a batch of symmetric matrices that live in a caller's workspace, the
+// bounds of the tridiagonal's spectrum and one eigenvalue of it by Sturm-count bisection.
+// Internal: included by those translation units only, everything in an anonymous namespace.
 //
-// Every sum has a fixed order (tile outputs: one FMA chain over k ascending; means: rows ascending, then one division;
-// block reductions: one fixed tree), so a problem's result does not depend on the batch it is part of, and the two
+// Every sum has a fixed order (tile outputs: one FMA chain over k ascending; means: rows ascending, then one
+// division; block reductions: one fixed tree), so a problem's result does not depend on the batch it is part of, and the
 // stages cannot drift apart.
 #ifndef DT_DENSE64_H
 #define DT_DENSE64_H
@@ -42,6 +43,27 @@ inline bool aligned16(const void *ptr, long long s1, long long s2) {
 
 // bytes of the int flags (non-finite input, status) at the head of a workspace, rounded to 256
 __host__ __device__ inline size_t flag_head_bytes(int count) { return ((size_t)count * sizeof(int) + 255) / 256 * 256; }
+
+// What the set-pair entries (dt_fid_distance, dt_fid_cov_distance, dt_quality_scores, dt_quality_stream_scores) do once
+// their own null and shape tests have passed, in this order: a negative stride is DT_E_SHAPE, rows or a workspace that the
+// float4 / double accesses cannot take DT_E_ARG, a workspace shorter than `need` bytes DT_E_WORKSPACE; with rc == DT_OK the
+// rows, the flags at the head of the workspace (`head` bytes, flag_head_bytes) and the doubles after them.
+struct SetPair {
+  int rc;
+  Rows R;
+  int *flag;
+  double *wd;
+};
+
+inline SetPair set_pair_open(const float *a, int n_a, long long a_ps, long long a_rs, const float *b, int n_b,
+                             long long b_ps, long long b_rs, void *ws, size_t ws_bytes, size_t need, size_t head) {
+  const Rows R{a, b, a_ps, a_rs, b_ps, b_rs, n_a, n_b};
+  int rc = DT_OK;
+  if (a_ps < 0 || b_ps < 0 || a_rs < 0 || b_rs < 0) rc = DT_E_SHAPE;
+  else if (!aligned16(a, a_ps, a_rs) || !aligned16(b, b_ps, b_rs) || ((uintptr_t)ws & 15)) rc = DT_E_ARG;
+  else if (ws_bytes < need) rc = DT_E_WORKSPACE;
+  return SetPair{rc, R, (int *)ws, (double *)((char *)ws + head)};
+}
 
 // one set of problem p: first row, row stride, count (a loop over one set steps a pointer; row_ptr would choose per row)
 struct RowSet {
@@ -149,6 +171,10 @@ __device__ inline void store_tile(double *C, int nr, int nc, int bi, int bj, con
       }
     }
 }
+
+// the accumulator of v_mfma_f64_16x16x4_f64: cov_gram_kernel (dt_fid.hip) and gram_tile (dt_quality_stream.hip) each keep
+// their own stage loop on it -- one shared routine was measured and cost the panel route its stage times
+typedef double mfma_acc __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------------------------------------- tridiagonalisation
 // Unblocked, dsytd2-like, lower: one reflector, one matrix-vector product and one symmetric rank-2 update per column,

@@ -392,9 +392,7 @@ __global__ __launch_bounds__(kThreads) void cov_stats_kernel(int n_a, int n_b, i
 // of every output to its accumulator, which lies at column l % 16, rows l / 16 + 4 i of the block.  Every output of
 // every tile runs through the same sequence of instructions on a_k,i a_k,j, and the product commutes, so C[i][j] and
 // C[j][i] of a diagonal tile are the same bits.  The same tile on plain fp64 FMAs (the inner loop of tile_product) was
-// measured beside this one and dropped: 1.5 times slower at D = 2048.
-typedef double mfma_acc __attribute__((ext_vector_type(4)));
-
+// measured beside this one and dropped: 1.5 times slower at D = 2048.  mfma_acc: dt_dense64.h.
 __global__ __launch_bounds__(kThreads) void cov_gram_kernel(Rows R, int D, CovLayout L, double *ws, const int *flag,
                                                             int nt, int tiles) {
   __shared__ double As[16][64], Bs[16][64];
@@ -643,16 +641,13 @@ extern "C" int dt_fid_distance(const float *a_dev, int n_a, long long a_pstride,
                                double *fid_dev, double *parts_dev, int *status_dev, void *ws, size_t ws_bytes,
                                void *const *events, void *stream) {
   if (!a_dev || !b_dev || !fid_dev || !parts_dev || !status_dev || !ws) return DT_E_NULL;
-  if (!shape_ok(P, n_a, n_b, D) || a_pstride < 0 || b_pstride < 0 || a_rstride < 0 || b_rstride < 0) return DT_E_SHAPE;
-  if (!aligned16(a_dev, a_pstride, a_rstride) || !aligned16(b_dev, b_pstride, b_rstride) || ((uintptr_t)ws & 15))
-    return DT_E_ARG;
+  if (!shape_ok(P, n_a, n_b, D)) return DT_E_SHAPE;
   const Layout L(P, n_a, n_b, D);
-  if (ws_bytes < L.bytes(P)) return DT_E_WORKSPACE;
+  const auto [rc, R, flag, wd] = set_pair_open(a_dev, n_a, a_pstride, a_rstride, b_dev, n_b, b_pstride, b_rstride, ws,
+                                               ws_bytes, L.bytes(P), L.head);
+  if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   if (events) DT_HIP_TRY(hipEventRecord((hipEvent_t)events[0], s));
-  const Rows R{a_dev, b_dev, a_pstride, a_rstride, b_pstride, b_rstride, n_a, n_b};
-  int *flag = (int *)ws;
-  double *wd = (double *)((char *)ws + L.head);
   const int m = L.m;
   DT_HIP_TRY(hipMemsetAsync(ws, 0, L.head, s));
   fid_mean_kernel<<<dim3((D / 4 + kWave - 1) / kWave, P, 2), kWave, 0, s>>>(R, D, wd, L.per, flag);
@@ -689,17 +684,13 @@ extern "C" int dt_fid_cov_distance(const float *a_dev, int n_a, long long a_pstr
                                    double *fid_dev, double *parts_dev, int *status_dev, void *ws, size_t ws_bytes,
                                    void *const *events, void *stream) {
   if (!a_dev || !b_dev || !fid_dev || !parts_dev || !status_dev || !ws) return DT_E_NULL;
-  if (!cov_shape_ok(P, n_a, n_b, D) || a_pstride < 0 || b_pstride < 0 || a_rstride < 0 || b_rstride < 0)
-    return DT_E_SHAPE;
-  if (!aligned16(a_dev, a_pstride, a_rstride) || !aligned16(b_dev, b_pstride, b_rstride) || ((uintptr_t)ws & 15))
-    return DT_E_ARG;
+  if (!cov_shape_ok(P, n_a, n_b, D)) return DT_E_SHAPE;
   const CovLayout L(P, n_a, n_b, D);
-  if (ws_bytes < L.bytes(P)) return DT_E_WORKSPACE;
+  const auto [rc, R, flag, wd] = set_pair_open(a_dev, n_a, a_pstride, a_rstride, b_dev, n_b, b_pstride, b_rstride, ws,
+                                               ws_bytes, L.bytes(P), L.head);
+  if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   if (events) DT_HIP_TRY(hipEventRecord((hipEvent_t)events[0], s));
-  const Rows R{a_dev, b_dev, a_pstride, a_rstride, b_pstride, b_rstride, n_a, n_b};
-  int *flag = (int *)ws;
-  double *wd = (double *)((char *)ws + L.head);
   DT_HIP_TRY(hipMemsetAsync(ws, 0, L.head, s));
   const int nqb = (D / 4 + kWave - 1) / kWave, ncmax = L.nc[0] > L.nc[1] ? L.nc[0] : L.nc[1];
   cov_colsum_kernel<<<dim3(nqb * ncmax, P, 2), kWave, 0, s>>>(R, D, L, wd, flag, nqb);

@@ -6,14 +6,14 @@
 //   1. G_AA, G_BB (upper-triangle tiles, mirrored) and G_AB, 64 x 64 tiles of the shared tile_product over the un-centred
 //      rows (quality_gram_kernel); their diagonals, and the non-finite flag read off them: a row's G(x, x) is finite
 //      exactly when the row is (quality_diag_kernel);
-//   2. the squared radii: one wave per row of d2(A, A) / d2(B, B), the row's distances as 63-bit keys in LDS (a
-//      non-negative double orders as its bit pattern) and the (k+1)-th smallest built bit by bit from the top, each
-//      bit one count over the row -- 63 passes whatever k is (quality_radius_kernel);
+//   2. the squared radii: one wave per row of d2(A, A) / d2(B, B), the row's distances as 63-bit keys in LDS and the
+//      (k+1)-th smallest of them (select_key, dt_quality_math.h) (quality_radius_kernel);
 //   3. the counts: one wave per row of d2(A, B) (recall, density, coverage) and one per column (precision), per-row
 //      integers without atomics (quality_count_kernel);
 //   4. the row sums of kappa, one wave per row of each matrix (quality_kappa_kernel), the subsets' sums gathered from
 //      the same matrices (quality_subset_kernel), and the fixed trees, KID, counts, radii and status
 //      (quality_finish_kernel).
+// The work of a wave on a Gram row and the finish are those of dt_quality_math.h, shared with dt_quality_stream.hip.
 #include <math.h>
 
 #include "../../include/dt_hip_quality.h"
@@ -25,18 +25,15 @@ namespace {
 // per-problem workspace (doubles), after a head of P ints (the non-finite flag) rounded to 256 bytes
 struct Layout {
   size_t head, per;
-  size_t GAA, GBB, GAB, diag, r2, rs, hits;
+  size_t GAA, GBB, GAB;
+  ScoreTail tail;
   __host__ __device__ Layout(int P, int n_a, int n_b) {
     head = flag_head_bytes(P);
     const size_t na = (size_t)n_a, nb = (size_t)n_b;
     GAA = 0;                          // [n_a][n_a]
     GBB = GAA + na * na;              // [n_b][n_b]
     GAB = GBB + nb * nb;              // [n_a][n_b]
-    diag = GAB + na * nb;             // G(a_i, a_i), then G(b_j, b_j)
-    r2 = diag + na + nb;              // squared radii, A's then B's
-    rs = r2 + na + nb;                // kappa row sums: A x A, B x B, A x B
-    hits = rs + 2 * na + nb;          // ints: recall flag [n_a], density count [n_a], precision flag [n_b]
-    per = hits + (2 * na + nb + 1) / 2;
+    per = tail.place(GAB + na * nb, na, nb);
   }
   __host__ __device__ size_t bytes(int P) const { return head + (size_t)P * per * sizeof(double); }
 };
@@ -83,7 +80,7 @@ __global__ __launch_bounds__(kThreads) void quality_diag_kernel(int n_a, int n_b
   bool bad = false;
   for (int i = threadIdx.x; i < n_a + n_b; i += kThreads) {
     const double g = i < n_a ? base[L.GAA + (size_t)i * n_a + i] : base[L.GBB + (size_t)(i - n_a) * n_b + (i - n_a)];
-    base[L.diag + i] = g;
+    base[L.tail.diag + i] = g;
     bad |= !isfinite(g);
   }
   if (bad) atomicOr(&bad_s, 1);
@@ -103,20 +100,12 @@ __global__ __launch_bounds__(kWave) void quality_radius_kernel(int n_a, int n_b,
   const bool second = (int)blockIdx.x >= n_a;
   const int i = second ? blockIdx.x - n_a : blockIdx.x, n = second ? n_b : n_a;
   const double *G = base + (second ? L.GBB : L.GAA) + (size_t)i * n;
-  const double *dg = base + L.diag + (second ? n_a : 0);
+  const double *dg = base + L.tail.diag + (second ? n_a : 0);
   const double gi = dg[i];
-  for (int j = threadIdx.x; j < n; j += kWave)
-    key[j] = (unsigned long long)__double_as_longlong(dist2(gi, dg[j], G[j])) & 0x7fffffffffffffffull;
+  for (int j = threadIdx.x; j < n; j += kWave) key[j] = dist2_key(gi, dg[j], G[j]);
   __syncthreads();
-  // the largest r with fewer than k + 1 keys below it: the (k+1)-th smallest key
-  unsigned long long r = 0;
-  for (int bit = 62; bit >= 0; --bit) {
-    const unsigned long long trial = r | (1ull << bit);
-    int below = 0;
-    for (int j = threadIdx.x; j < n; j += kWave) below += key[j] < trial;
-    if (wave_sum_int(below) <= k) r = trial;
-  }
-  if (threadIdx.x == 0) base[L.r2 + blockIdx.x] = __longlong_as_double((long long)r);
+  const unsigned long long r = select_key(key, n, k);
+  if (threadIdx.x == 0) base[L.tail.r2 + blockIdx.x] = __longlong_as_double((long long)r);
 }
 
 // ---------------------------------------------------------------------------------------------- 3. counts
@@ -128,23 +117,11 @@ __global__ __launch_bounds__(kWave) void quality_count_kernel(int n_a, int n_b, 
   if (flag[p]) return;
   const Layout L(0, n_a, n_b);
   double *base = ws + (size_t)p * per;
-  const double *ga = base + L.diag, *gb = ga + n_a, *ra = base + L.r2, *rb = ra + n_a, *G = base + L.GAB;
-  int *hits = reinterpret_cast<int *>(base + L.hits);
+  const double *ga = base + L.tail.diag, *gb = ga + n_a, *ra = base + L.tail.r2, *rb = ra + n_a, *G = base + L.GAB;
+  int *hits = reinterpret_cast<int *>(base + L.tail.hits);
   if ((int)blockIdx.x < n_a) {
     const int i = blockIdx.x;
-    const double gi = ga[i], ri = ra[i];
-    int within = 0, reached = 0;
-    for (int j = threadIdx.x; j < n_b; j += kWave) {
-      const double d = dist2(gi, gb[j], G[(size_t)i * n_b + j]);
-      within += d < ri;
-      reached |= d < rb[j];
-    }
-    within = wave_sum_int(within);
-    reached = wave_sum_int(reached) != 0;
-    if (threadIdx.x == 0) {
-      hits[i] = reached;
-      hits[n_a + i] = within;
-    }
+    count_row(G + (size_t)i * n_b, n_b, ga[i], ra[i], gb, rb, hits + i, hits + n_a + i);
   } else {
     const int j = blockIdx.x - n_a;
     const double gj = gb[j];
@@ -156,8 +133,7 @@ __global__ __launch_bounds__(kWave) void quality_count_kernel(int n_a, int n_b, 
 }
 
 // ---------------------------------------------------------------------------------------------- 4. kernel sums
-// blockIdx.x: rows of G_AA, rows of G_BB (both without their diagonal entry), rows of G_AB; lanes over the columns in
-// ascending order, then the butterfly
+// blockIdx.x: rows of G_AA, rows of G_BB (both without their diagonal entry), rows of G_AB (kappa_row_sum)
 __global__ __launch_bounds__(kWave) void quality_kappa_kernel(int n_a, int n_b, int D, double *ws, size_t per,
                                                               const int *flag) {
   const int p = blockIdx.y;
@@ -170,12 +146,8 @@ __global__ __launch_bounds__(kWave) void quality_kappa_kernel(int n_a, int n_b, 
   if (x < n_a) { n = n_a; G = base + L.GAA + (size_t)x * n_a; skip = x; }
   else if (x < n_a + n_b) { n = n_b; G = base + L.GBB + (size_t)(x - n_a) * n_b; skip = x - n_a; }
   else { n = n_b; G = base + L.GAB + (size_t)(x - n_a - n_b) * n_b; }
-  const double dd = (double)D;
-  double s = 0.0;
-  for (int j = threadIdx.x; j < n; j += kWave)
-    if (j != skip) s += kappa(G[j], dd);
-  s = wave_sum(s);
-  if (threadIdx.x == 0) base[L.rs + x] = s;
+  const double s = kappa_row_sum(G, n, skip, (double)D);
+  if (threadIdx.x == 0) base[L.tail.rs + x] = s;
 }
 
 // One workgroup per (subset, problem): wave w takes the subset's rows w, w + 4, ..., lanes over its columns, and adds
@@ -228,56 +200,9 @@ __global__ __launch_bounds__(kThreads) void quality_subset_kernel(int n_a, int n
 __global__ __launch_bounds__(kThreads) void quality_finish_kernel(int n_a, int n_b, int S, const double *ws, size_t per,
                                                                   const int *flag, double *kid_out, long long *counts_out,
                                                                   double *radii_out, int *status_out) {
-  __shared__ double red[kThreads];
-  __shared__ long long redi[kThreads];
-  const int p = blockIdx.x, t = threadIdx.x;
-  double *kid = kid_out + (size_t)p * (1 + S);
-  long long *counts = counts_out + 4 * (size_t)p;
-  double *radii = radii_out ? radii_out + (size_t)p * (n_a + n_b) : nullptr;
-  if (flag[p]) {
-    if (radii)
-      for (int i = t; i < n_a + n_b; i += kThreads) radii[i] = NAN;
-    if (t == 0) {
-      kid[0] = NAN;                        // the subsets' entries: quality_subset_kernel
-      counts[0] = counts[1] = counts[2] = counts[3] = -1;
-      status_out[p] = DT_QUALITY_NONFINITE;
-    }
-    return;
-  }
   const Layout L(0, n_a, n_b);
-  const double *base = ws + (size_t)p * per;
-  const double *rs = base + L.rs;
-  const int *hits = reinterpret_cast<const int *>(base + L.hits);
-  double saa = 0.0, sbb = 0.0, sab = 0.0;
-  long long recall = 0, density = 0, coverage = 0, precision = 0;
-  for (int i = t; i < n_a; i += kThreads) {
-    saa += rs[i];
-    sab += rs[n_a + n_b + i];
-    recall += hits[i];
-    density += hits[n_a + i];
-    coverage += hits[n_a + i] > 0;
-  }
-  for (int j = t; j < n_b; j += kThreads) {
-    sbb += rs[n_a + j];
-    precision += hits[2 * n_a + j];
-  }
-  saa = block_sum(saa, red);
-  sbb = block_sum(sbb, red);
-  sab = block_sum(sab, red);
-  precision = block_sum_int(precision, redi);
-  recall = block_sum_int(recall, redi);
-  density = block_sum_int(density, redi);
-  coverage = block_sum_int(coverage, redi);
-  if (radii)
-    for (int i = t; i < n_a + n_b; i += kThreads) radii[i] = base[L.r2 + i];
-  if (t == 0) {
-    kid[0] = kid_value(saa, sbb, sab, n_a, n_b);
-    counts[0] = precision;
-    counts[1] = recall;
-    counts[2] = density;
-    counts[3] = coverage;
-    status_out[p] = DT_QUALITY_OK;
-  }
+  const double *base = ws + (size_t)blockIdx.x * per;
+  score_finish(flag[blockIdx.x] != 0, n_a, n_b, L.tail, base, base, kid_out, 1 + S, counts_out, radii_out, status_out);
 }
 
 bool shape_ok(int P, int n_a, int n_b, int D) {
@@ -299,19 +224,16 @@ extern "C" int dt_quality_scores(const float *a_dev, int n_a, long long a_pstrid
                                  void *const *events, void *stream) {
   if (!a_dev || !b_dev || !kid_dev || !counts_dev || !status_dev || !ws) return DT_E_NULL;
   if (S > 0 && (!sub_a_dev || !sub_b_dev)) return DT_E_NULL;
-  if (!shape_ok(P, n_a, n_b, D) || a_pstride < 0 || b_pstride < 0 || a_rstride < 0 || b_rstride < 0) return DT_E_SHAPE;
+  if (!shape_ok(P, n_a, n_b, D)) return DT_E_SHAPE;
   const int n_min = n_a < n_b ? n_a : n_b;
   if (k < 1 || k > n_min - 1) return DT_E_SHAPE;
   if (S < 0 || S > DT_QUALITY_MAX_SUBSETS || (S > 0 && (m < 2 || m > n_min))) return DT_E_SHAPE;
-  if (!aligned16(a_dev, a_pstride, a_rstride) || !aligned16(b_dev, b_pstride, b_rstride) || ((uintptr_t)ws & 15))
-    return DT_E_ARG;
   const Layout L(P, n_a, n_b);
-  if (ws_bytes < L.bytes(P)) return DT_E_WORKSPACE;
+  const auto [rc, R, flag, wd] = set_pair_open(a_dev, n_a, a_pstride, a_rstride, b_dev, n_b, b_pstride, b_rstride, ws,
+                                               ws_bytes, L.bytes(P), L.head);
+  if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   if (events) DT_HIP_TRY(hipEventRecord((hipEvent_t)events[0], s));
-  const Rows R{a_dev, b_dev, a_pstride, a_rstride, b_pstride, b_rstride, n_a, n_b};
-  int *flag = (int *)ws;
-  double *wd = (double *)((char *)ws + L.head);
   const int nta = (n_a + 63) / 64, ntb = (n_b + 63) / 64;
   quality_gram_kernel<<<dim3(nta * (nta + 1) / 2 + ntb * (ntb + 1) / 2 + nta * ntb, P), kThreads, 0, s>>>(R, D, wd, L.per,
                                                                                                         nta, ntb);

@@ -16,6 +16,8 @@
 //      precision flag OR-ed into its word (qstream_count_cols_kernel);
 //   5. the fixed trees, KID, counts, radii and status (qstream_finish_kernel).
 // With a shared teacher (a_pstride == 0, P > 1) the A side lives in problem 0's part of the workspace and is formed once.
+// The work of a wave on a Gram row and the finish are those of dt_quality_math.h, shared with dt_quality.hip: the same
+// definitions and the same orders of summation because they are the same functions.
 #include <math.h>
 
 #include "../../include/dt_hip_quality_stream.h"
@@ -30,16 +32,13 @@ constexpr int kStep = 4 * kWave;   // keys a wave takes per step of the stream
 // per-problem workspace (doubles), after a head of 2 P ints (the non-finite flags of A and of B) rounded to 256 bytes
 struct Layout {
   size_t head, per;
-  size_t panel, diag, r2, rs, hits;
+  size_t panel;
+  ScoreTail tail;
   __host__ __device__ Layout(int P, int n_a, int n_b, int panel_rows) {
     head = flag_head_bytes(2 * P);
     const size_t na = (size_t)n_a, nb = (size_t)n_b;
-    panel = 0;                                         // [panel_rows][columns of the matrix the panel is of]
-    diag = panel + (size_t)panel_rows * (na > nb ? na : nb);   // G(a_i, a_i), then G(b_j, b_j)
-    r2 = diag + na + nb;                               // squared radii, A's then B's
-    rs = r2 + na + nb;                                 // kappa row sums: A x A, B x B, A x B
-    hits = rs + 2 * na + nb;                           // ints: recall flag [n_a], density count [n_a], precision flag [n_b]
-    per = hits + (2 * na + nb + 1) / 2;
+    panel = 0;                        // [panel_rows][columns of the matrix the panel is of]
+    per = tail.place(panel + (size_t)panel_rows * (na > nb ? na : nb), na, nb);
   }
   __host__ __device__ size_t bytes(int P) const { return head + (size_t)P * per * sizeof(double); }
 };
@@ -69,8 +68,6 @@ __device__ inline bool bad_problem(const Job &J, int p) { return (J.flag[2 * p] 
 // and the product commutes.  So two rows give the same bits wherever they meet: G(x, y) == G(y, x), and G(x, x) of the
 // diagonals (qstream_diag_kernel calls this function on the diagonal tiles) has the bits of the entry (x, x) of a panel
 // of A x A.  Hence the self-distance, and the distance of two bitwise-equal rows, is exactly 0.
-typedef double mfma_acc __attribute__((ext_vector_type(4)));
-
 __device__ inline void gram_tile(int D, const float *xrow, const float *yrow, mfma_acc (&acc)[4]) {
   __shared__ double Xs[16][64], Ys[16][64];
   const int t = threadIdx.x, lr = t / 4, kq = 4 * (t % 4);
@@ -118,7 +115,7 @@ __global__ __launch_bounds__(kThreads) void qstream_diag_kernel(Job J, int nta) 
   const float *src = row < n ? set_row(J.R, set, p, row) : nullptr;
   mfma_acc acc[4] = {};
   gram_tile(J.D, src, src, acc);
-  double *diag = part_of(J, p) + J.L.diag + (second ? J.R.n_a : 0);
+  double *diag = part_of(J, p) + J.L.tail.diag + (second ? J.R.n_a : 0);
   const int w = threadIdx.x / 64, lane = threadIdx.x % 64, lk = lane / 16, lc = lane % 16;
 #pragma unroll
   for (int j = 0; j < 4; ++j)
@@ -136,7 +133,7 @@ __global__ __launch_bounds__(kThreads) void qstream_flag_kernel(Job J) {
   const int p = blockIdx.x, n_a = J.R.n_a, n_b = J.R.n_b;
   if (threadIdx.x < 2) bad_s[threadIdx.x] = 0;
   __syncthreads();
-  const double *da = a_part_of(J, p) + J.L.diag, *db = part_of(J, p) + J.L.diag + n_a;
+  const double *da = a_part_of(J, p) + J.L.tail.diag, *db = part_of(J, p) + J.L.tail.diag + n_a;
   bool bad_a = false, bad_b = false;
   for (int i = threadIdx.x; i < n_a; i += kThreads) bad_a |= !isfinite(da[i]);
   for (int j = threadIdx.x; j < n_b; j += kThreads) bad_b |= !isfinite(db[j]);
@@ -171,26 +168,13 @@ __global__ __launch_bounds__(kThreads) void qstream_gram_kernel(Job J, int xs, i
 }
 
 // ---------------------------------------------------------------------------------------------- 2. radii
-// The (k+1)-th smallest of buf[0 .. count), count > k: the largest r with fewer than k + 1 keys below it, built bit by bit
-// from the top, each bit one count over the buffer (the selection of quality_radius_kernel).  One wave.
-__device__ inline unsigned long long select_key(const unsigned long long *buf, int count, int k) {
-  unsigned long long r = 0;
-  for (int bit = 62; bit >= 0; --bit) {
-    const unsigned long long trial = r | (1ull << bit);
-    int below = 0;
-    for (int j = threadIdx.x; j < count; j += kWave) below += buf[j] < trial;
-    if (wave_sum_int(below) <= k) r = trial;
-  }
-  return r;
-}
-
-// One wave per row of the panel of d2(A, A) (set 0) or d2(B, B) (set 1); a key is the 63-bit pattern of dist2 (a
-// non-negative double orders as its bit pattern).  The wave keeps a threshold T, at first above every key, and appends
-// a key to the LDS buffer only if it is < T.  When the buffer cannot take another step's keys, t = the (k+1)-th smallest
-// of the buffer becomes T and the buffer shrinks to its keys < t (at most k) plus as many copies of t as make k + 1
-// entries.  A dropped key is >= T, and at least k + 1 entries <= T stay in the buffer, so the (k+1)-th smallest of the
-// buffer is always that of the keys seen so far, duplicates counted: the result is exact and depends on nothing but the
-// row's keys.  k + 1 <= 1024 entries leave room for a step after every refill.
+// One wave per row of the panel of d2(A, A) (set 0) or d2(B, B) (set 1); a key is dist2_key (dt_quality_math.h).  The
+// wave keeps a threshold T, at first above every key, and appends a key to the LDS buffer only if it is < T.  When the
+// buffer cannot take another step's keys, t = the (k+1)-th smallest of the buffer (select_key) becomes T and the buffer
+// shrinks to its keys < t (at most k) plus as many copies of t as make k + 1 entries.  A dropped key is >= T, and at
+// least k + 1 entries <= T stay in the buffer, so the (k+1)-th smallest of the buffer is always that of the keys seen so
+// far, duplicates counted: the result is exact and depends on nothing but the row's keys.  k + 1 <= 1024 entries leave
+// room for a step after every refill.
 __global__ __launch_bounds__(kWave) void qstream_select_kernel(Job J, int set, int r0) {
   __shared__ unsigned long long buf[kBuf];
   const int p = blockIdx.y;
@@ -199,7 +183,7 @@ __global__ __launch_bounds__(kWave) void qstream_select_kernel(Job J, int set, i
   double *base = part_of(J, p);
   const int i = r0 + blockIdx.x, lane = threadIdx.x;
   const double *G = base + J.L.panel + (size_t)blockIdx.x * n;
-  const double *dg = base + J.L.diag + off;
+  const double *dg = base + J.L.tail.diag + off;
   const double gi = dg[i];
   const unsigned long long none = ~0ull, below_me = (1ull << lane) - 1;
   unsigned long long T = none;
@@ -225,7 +209,7 @@ __global__ __launch_bounds__(kWave) void qstream_select_kernel(Job J, int set, i
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int j = j0 + kWave * u + lane;
-      key[u] = j < n ? (unsigned long long)__double_as_longlong(dist2(gi, dg[j], G[j])) & 0x7fffffffffffffffull : none;
+      key[u] = j < n ? dist2_key(gi, dg[j], G[j]) : none;
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -237,30 +221,24 @@ __global__ __launch_bounds__(kWave) void qstream_select_kernel(Job J, int set, i
   }
   __syncthreads();
   const unsigned long long r = select_key(buf, count, k);
-  if (lane == 0) base[J.L.r2 + off + i] = __longlong_as_double((long long)r);
+  if (lane == 0) base[J.L.tail.r2 + off + i] = __longlong_as_double((long long)r);
 }
 
 // ---------------------------------------------------------------------------------------------- 3. kernel sums
-// One wave per row of the panel; kind 0: A x A, 1: B x B (both without the diagonal entry, skipped by index), 2: A x B.
-// Lanes over the columns in ascending order, then the butterfly: a row's sum does not depend on the panel it fell into.
+// One wave per row of the panel; kind 0: A x A, 1: B x B (both without the diagonal entry, skipped by index), 2: A x B
+// (kappa_row_sum: a row's sum does not depend on the panel it fell into).
 __global__ __launch_bounds__(kWave) void qstream_kappa_kernel(Job J, int kind, int r0) {
   const int p = blockIdx.y;
   if (J.flag[2 * p] | (kind ? J.flag[2 * p + 1] : 0)) return;
   const int n_a = J.R.n_a, n_b = J.R.n_b, n = kind ? n_b : n_a;
   double *base = part_of(J, p);
   const int i = r0 + blockIdx.x, skip = kind < 2 ? i : -1;
-  const double *G = base + J.L.panel + (size_t)blockIdx.x * n;
-  const double dd = (double)J.D;
-  double s = 0.0;
-  for (int j = threadIdx.x; j < n; j += kWave)
-    if (j != skip) s += kappa(G[j], dd);
-  s = wave_sum(s);
-  if (threadIdx.x == 0) base[J.L.rs + (kind == 0 ? 0 : kind == 1 ? n_a : n_a + n_b) + i] = s;
+  const double s = kappa_row_sum(base + J.L.panel + (size_t)blockIdx.x * n, n, skip, (double)J.D);
+  if (threadIdx.x == 0) base[J.L.tail.rs + (kind == 0 ? 0 : kind == 1 ? n_a : n_a + n_b) + i] = s;
 }
 
 // ---------------------------------------------------------------------------------------------- 4. counts
-// One wave per row i of the panel of A x B: whether some b_j has a_i within its radius (recall) and how many b_j lie
-// within a_i's (density; coverage is whether any does).
+// One wave per row i of the panel of A x B: the recall flag and the density count (count_row).
 __global__ __launch_bounds__(kWave) void qstream_count_rows_kernel(Job J, int r0) {
   const int p = blockIdx.y;
   if (bad_problem(J, p)) return;
@@ -268,22 +246,9 @@ __global__ __launch_bounds__(kWave) void qstream_count_rows_kernel(Job J, int r0
   double *base = part_of(J, p);
   const double *abase = a_part_of(J, p);
   const int i = r0 + blockIdx.x;
-  const double *G = base + J.L.panel + (size_t)blockIdx.x * n_b;
-  const double *gb = base + J.L.diag + n_a, *rb = base + J.L.r2 + n_a;
-  const double gi = abase[J.L.diag + i], ri = abase[J.L.r2 + i];
-  int *hits = reinterpret_cast<int *>(base + J.L.hits);
-  int within = 0, reached = 0;
-  for (int j = threadIdx.x; j < n_b; j += kWave) {
-    const double d = dist2(gi, gb[j], G[j]);
-    within += d < ri;
-    reached |= d < rb[j];
-  }
-  within = wave_sum_int(within);
-  reached = wave_sum_int(reached) != 0;
-  if (threadIdx.x == 0) {
-    hits[i] = reached;
-    hits[n_a + i] = within;
-  }
+  int *hits = reinterpret_cast<int *>(base + J.L.tail.hits);
+  count_row(base + J.L.panel + (size_t)blockIdx.x * n_b, n_b, abase[J.L.tail.diag + i], abase[J.L.tail.r2 + i],
+            base + J.L.tail.diag + n_a, base + J.L.tail.r2 + n_a, hits + i, hits + n_a + i);
 }
 
 // 64 columns of the panel of A x B per workgroup: wave w takes the panel's rows w, w + 4, ... (a wave reads 64
@@ -297,75 +262,29 @@ __global__ __launch_bounds__(kThreads) void qstream_count_cols_kernel(Job J, int
   const int n_a = J.R.n_a, n_b = J.R.n_b;
   double *base = part_of(J, p);
   const double *abase = a_part_of(J, p);
-  const double *ga = abase + J.L.diag, *ra = abase + J.L.r2, *G = base + J.L.panel;
+  const double *ga = abase + J.L.tail.diag, *ra = abase + J.L.tail.r2, *G = base + J.L.panel;
   const int w = threadIdx.x / kWave, lane = threadIdx.x % kWave, j = blockIdx.x * kWave + lane;
   int reached = 0;
   if (j < n_b) {
-    const double gj = base[J.L.diag + n_a + j];
+    const double gj = base[J.L.tail.diag + n_a + j];
     for (int r = w; r < rows; r += kThreads / kWave)
       reached |= dist2(ga[r0 + r], gj, G[(size_t)r * n_b + j]) < ra[r0 + r];
   }
   part[w][lane] = reached;
   __syncthreads();
   if (w == 0 && j < n_b) {
-    int *word = reinterpret_cast<int *>(base + J.L.hits) + 2 * n_a + j;
+    int *word = reinterpret_cast<int *>(base + J.L.tail.hits) + 2 * n_a + j;
     const int all = part[0][lane] | part[1][lane] | part[2][lane] | part[3][lane];
     *word = r0 == 0 ? all : (*word | all);
   }
 }
 
 // ---------------------------------------------------------------------------------------------- 5. finish
-// the order of quality_finish_kernel
 __global__ __launch_bounds__(kThreads) void qstream_finish_kernel(Job J, double *kid_out, long long *counts_out,
                                                                   double *radii_out, int *status_out) {
-  __shared__ double red[kThreads];
-  __shared__ long long redi[kThreads];
-  const int p = blockIdx.x, t = threadIdx.x, n_a = J.R.n_a, n_b = J.R.n_b;
-  long long *counts = counts_out + 4 * (size_t)p;
-  double *radii = radii_out ? radii_out + (size_t)p * (n_a + n_b) : nullptr;
-  if (bad_problem(J, p)) {
-    if (radii)
-      for (int i = t; i < n_a + n_b; i += kThreads) radii[i] = NAN;
-    if (t == 0) {
-      kid_out[p] = NAN;
-      counts[0] = counts[1] = counts[2] = counts[3] = -1;
-      status_out[p] = DT_QUALITY_NONFINITE;
-    }
-    return;
-  }
-  const double *base = part_of(J, p), *abase = a_part_of(J, p);
-  const double *rs = base + J.L.rs, *rsa = abase + J.L.rs;
-  const int *hits = reinterpret_cast<const int *>(base + J.L.hits);
-  double saa = 0.0, sbb = 0.0, sab = 0.0;
-  long long recall = 0, density = 0, coverage = 0, precision = 0;
-  for (int i = t; i < n_a; i += kThreads) {
-    saa += rsa[i];
-    sab += rs[n_a + n_b + i];
-    recall += hits[i];
-    density += hits[n_a + i];
-    coverage += hits[n_a + i] > 0;
-  }
-  for (int j = t; j < n_b; j += kThreads) {
-    sbb += rs[n_a + j];
-    precision += hits[2 * n_a + j];
-  }
-  saa = block_sum(saa, red);
-  sbb = block_sum(sbb, red);
-  sab = block_sum(sab, red);
-  precision = block_sum_int(precision, redi);
-  recall = block_sum_int(recall, redi);
-  density = block_sum_int(density, redi);
-  coverage = block_sum_int(coverage, redi);
-  if (radii)
-    for (int i = t; i < n_a + n_b; i += kThreads) radii[i] = (i < n_a ? abase : base)[J.L.r2 + i];
-  if (t == 0) {
-    kid_out[p] = kid_value(saa, sbb, sab, n_a, n_b);
-    counts[0] = precision;
-    counts[1] = recall;
-    counts[2] = density;
-    counts[3] = coverage;
-    status_out[p] = DT_QUALITY_OK;
-  }
+  const int p = blockIdx.x;
+  score_finish(bad_problem(J, p), J.R.n_a, J.R.n_b, J.L.tail, a_part_of(J, p), part_of(J, p), kid_out, 1, counts_out,
+               radii_out, status_out);
 }
 
 bool shape_ok(int P, int n_a, int n_b, int D, int panel_rows) {
@@ -387,19 +306,17 @@ extern "C" int dt_quality_stream_scores(const float *a_dev, int n_a, long long a
                                         double *radii_dev, int *status_dev, void *ws, size_t ws_bytes,
                                         void *const *events, void *stream) {
   if (!a_dev || !b_dev || !kid_dev || !counts_dev || !status_dev || !ws) return DT_E_NULL;
-  if (!shape_ok(P, n_a, n_b, D, panel_rows) || a_pstride < 0 || b_pstride < 0 || a_rstride < 0 || b_rstride < 0)
-    return DT_E_SHAPE;
+  if (!shape_ok(P, n_a, n_b, D, panel_rows)) return DT_E_SHAPE;
   const int n_min = n_a < n_b ? n_a : n_b;
   if (k < 1 || k > n_min - 1 || k > DT_QUALITY_STREAM_MAX_K) return DT_E_SHAPE;
-  if (!aligned16(a_dev, a_pstride, a_rstride) || !aligned16(b_dev, b_pstride, b_rstride) || ((uintptr_t)ws & 15))
-    return DT_E_ARG;
   const Layout L(P, n_a, n_b, panel_rows);
-  if (ws_bytes < L.bytes(P)) return DT_E_WORKSPACE;
+  const auto [rc, R, flag, wd] = set_pair_open(a_dev, n_a, a_pstride, a_rstride, b_dev, n_b, b_pstride, b_rstride, ws,
+                                               ws_bytes, L.bytes(P), L.head);
+  if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   if (events) DT_HIP_TRY(hipEventRecord((hipEvent_t)events[0], s));
   const int ash = a_pstride == 0 && P > 1;
-  const Job J{Rows{a_dev, b_dev, a_pstride, a_rstride, b_pstride, b_rstride, n_a, n_b}, L, (double *)((char *)ws + L.head),
-              (int *)ws, D, k, ash};
+  const Job J{R, L, wd, flag, D, k, ash};
   const int nta = (n_a + 63) / 64, ntb = (n_b + 63) / 64;
   qstream_diag_kernel<<<dim3(nta + ntb, P), kThreads, 0, s>>>(J, nta);
   DT_LAUNCH_CHECK();

@@ -9,6 +9,7 @@ import ctypes
 import math
 import os
 import sys
+import types
 from ctypes import c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
 
 import numpy as np
@@ -1200,8 +1201,13 @@ def device_fid(a, b, events=None, workspace=None):
     return _fid_call(a, b, P, events, workspace, FID_EVENTS, "dt_fid_workspace_bytes", "dt_fid_distance")
 
 
-def _fid_call(a, b, P, events, workspace, n_events, query, entry):
-    """the checked sets through one of the two entries (they share the argument list) with that entry's workspace query"""
+def _set_pair_call(a, b, P, events, workspace, n_events, query, call, panel_rows=None):
+    """The checked sets (a, b, P) through one set-pair entry of the library: the events count, the devices, the rows as the
+    kernels read them, the workspace query ``query`` and the workspace.  ``panel_rows``: None, or ``lib -> rows`` for the
+    entry whose query takes that fifth argument.  ``call(c)`` makes the entry call and returns what the caller returns;
+    ``c`` holds ``lib``, ``dev``, ``rows`` (the entry's first ten arguments: a, n_a, its two strides, b, n_b, its two
+    strides, P, D), ``panel_rows`` (the resolved value or None) and ``tail`` (its last four: workspace, its bytes, events,
+    stream)."""
     if events is not None and len(events) != n_events:
         raise ValueError(f"events must be {n_events} torch.cuda.Event")
     _require_cuda(a, "a")
@@ -1212,12 +1218,11 @@ def _fid_call(a, b, P, events, workspace, n_events, query, entry):
     n_a, n_b, D = a.shape[-2], b.shape[-2], a.shape[-1]
     (a, a_ps, a_rs), (b, b_ps, b_rs) = _fid_rows(a), _fid_rows(b)
     dev = a.device
-    out = {"fid": torch.empty(P, dtype=torch.float64, device=dev),
-           "parts": torch.empty(P, 4, dtype=torch.float64, device=dev),
-           "status": torch.empty(P, dtype=torch.int32, device=dev)}
-    ws_bytes = getattr(lib, query)(P, n_a, n_b, D)
+    panel_rows = None if panel_rows is None else panel_rows(lib)
+    ws_bytes = getattr(lib, query)(P, n_a, n_b, D, *(() if panel_rows is None else (panel_rows,)))
     if ws_bytes == 0:
-        raise ValueError(f"{query} rejects P={P}, n_a={n_a}, n_b={n_b}, D={D}")
+        raise ValueError(f"{query} rejects P={P}, n_a={n_a}, n_b={n_b}, D={D}" +
+                         ("" if panel_rows is None else f", panel_rows={panel_rows}"))
     with torch.cuda.device(dev):
         ev = _stage_events(events)
         ws = workspace
@@ -1225,10 +1230,20 @@ def _fid_call(a, b, P, events, workspace, n_events, query, entry):
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         elif ws.dtype != torch.uint8 or ws.device != dev or not ws.is_contiguous() or ws.numel() < ws_bytes:
             raise ValueError(f"workspace must be a contiguous uint8 tensor of >= {ws_bytes} bytes on {dev}")
-        check(getattr(lib, entry)(ptr(a), n_a, a_ps, a_rs, ptr(b), n_b, b_ps, b_rs, P, D, ptr(out["fid"]),
-                                  ptr(out["parts"]), ptr(out["status"]), ptr(ws), ws_bytes, ev, stream_ptr()),
-              entry)
-    return out
+        return call(types.SimpleNamespace(lib=lib, dev=dev, panel_rows=panel_rows,
+                                          rows=(ptr(a), n_a, a_ps, a_rs, ptr(b), n_b, b_ps, b_rs, P, D),
+                                          tail=(ptr(ws), ws_bytes, ev, stream_ptr())))
+
+
+def _fid_call(a, b, P, events, workspace, n_events, query, entry):
+    """the checked sets through one of the two Fréchet entries (they share the argument list)"""
+    def call(c):
+        out = {"fid": torch.empty(P, dtype=torch.float64, device=c.dev),
+               "parts": torch.empty(P, 4, dtype=torch.float64, device=c.dev),
+               "status": torch.empty(P, dtype=torch.int32, device=c.dev)}
+        check(getattr(c.lib, entry)(*c.rows, ptr(out["fid"]), ptr(out["parts"]), ptr(out["status"]), *c.tail), entry)
+        return out
+    return _set_pair_call(a, b, P, events, workspace, n_events, query, call)
 
 
 # ---------------------------------------------------------------------- the feature-space route (include/dt_hip_fid_cov.h)
@@ -1288,6 +1303,15 @@ QUALITY_MAX_SUBSETS = 1024
 QUALITY_EVENTS = 5
 
 
+def _k_check(k, n_min, k_cap=None):
+    """k, the neighbour count of both routes: an integer in [1, n_min - 1], and at most k_cap on the row-panel route"""
+    k_max = n_min - 1
+    top = k_max if k_cap is None else min(k_max, k_cap)
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= top:
+        raise ValueError(f"k={k!r} must be an integer in [1, min(n_a, n_b) - 1] = [1, {k_max}]" +
+                         ("" if k_cap is None else f" and at most {k_cap} on the row-panel route"))
+
+
 def _quality_check(a, b, k):
     a, b, P = _set_pair(a, b)
     for t, name in ((a, "a"), (b, "b")):
@@ -1295,9 +1319,7 @@ def _quality_check(a, b, k):
             raise ValueError(f"{name} holds {t.shape[-2]} rows: the device sample-quality scores take 2 .. "
                              f"{QUALITY_MAX_ROWS} per set")
     _batch_limits(P, a.shape[-1])
-    n_min = min(a.shape[-2], b.shape[-2])
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= n_min - 1:
-        raise ValueError(f"k={k!r} must be an integer in [1, min(n_a, n_b) - 1] = [1, {n_min - 1}]")
+    _k_check(k, min(a.shape[-2], b.shape[-2]))
     return a, b, P
 
 
@@ -1342,45 +1364,36 @@ def device_quality(a, b, k=5, subsets=None, radii=False, events=None, workspace=
     a, b, P = _quality_check(a, b, k)
     n_a, n_b, D = a.shape[-2], b.shape[-2], a.shape[-1]
     tables = None if subsets is None else _quality_subsets(subsets, n_a, n_b)
-    if events is not None and len(events) != QUALITY_EVENTS:
-        raise ValueError(f"events must be {QUALITY_EVENTS} torch.cuda.Event")
-    _require_cuda(a, "a")
-    _require_cuda(b, "b")
-    if a.device != b.device:
-        raise ValueError(f"a is on {a.device}, b on {b.device}")
-    lib = _hip.load()
-    (a, a_ps, a_rs), (b, b_ps, b_rs) = _fid_rows(a), _fid_rows(b)
-    dev = a.device
     S, m = (0, 0) if tables is None else tables[0].shape
+
+    def call(c):
+        kid, counts, status, r2 = _quality_outputs(P, S, n_a, n_b, radii, c.dev)
+        sub = (None, None) if tables is None else tuple(torch.from_numpy(t).to(c.dev) for t in tables)
+        check(c.lib.dt_quality_scores(*c.rows, int(k), ptr(sub[0]), ptr(sub[1]), S, m, ptr(kid), ptr(counts), ptr(r2),
+                                      ptr(status), *c.tail), "dt_quality_scores")
+        return _quality_result(kid, counts, status, r2, n_a, n_b, int(k))
+    return _set_pair_call(a, b, P, events, workspace, QUALITY_EVENTS, "dt_quality_workspace_bytes", call)
+
+
+def _quality_outputs(P, S, n_a, n_b, radii, dev):
+    """(kid [P, 1 + S] fp64, counts [P, 4] int64, status [P] int32, squared radii [P, n_a + n_b] fp64 or None) for an
+    entry to fill"""
     f64 = dict(dtype=torch.float64, device=dev)
-    kid = torch.empty(P, 1 + S, **f64)
-    counts = torch.empty(P, 4, dtype=torch.int64, device=dev)
-    status = torch.empty(P, dtype=torch.int32, device=dev)
-    r2 = torch.empty(P, n_a + n_b, **f64) if radii else None
-    ws_bytes = lib.dt_quality_workspace_bytes(P, n_a, n_b, D)
-    if ws_bytes == 0:
-        raise ValueError(f"dt_quality_workspace_bytes rejects P={P}, n_a={n_a}, n_b={n_b}, D={D}")
-    with torch.cuda.device(dev):
-        sub = (None, None) if tables is None else tuple(torch.from_numpy(t).to(dev) for t in tables)
-        ev = _stage_events(events)
-        ws = workspace
-        if ws is None:
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        elif ws.dtype != torch.uint8 or ws.device != dev or not ws.is_contiguous() or ws.numel() < ws_bytes:
-            raise ValueError(f"workspace must be a contiguous uint8 tensor of >= {ws_bytes} bytes on {dev}")
-        check(lib.dt_quality_scores(ptr(a), n_a, a_ps, a_rs, ptr(b), n_b, b_ps, b_rs, P, D, int(k), ptr(sub[0]),
-                                    ptr(sub[1]), S, m, ptr(kid), ptr(counts), ptr(r2), ptr(status), ptr(ws), ws_bytes, ev,
-                                    stream_ptr()), "dt_quality_scores")
-        c = counts.to(torch.float64)
-        bad = counts[:, 0] < 0
-        out = {"kid": kid[:, 0], "kid_subsets": kid[:, 1:], "counts": counts, "status": status}
-        for name, col, den in (("precision", 0, n_b), ("recall", 1, n_a), ("density", 2, int(k) * n_b),
-                               ("coverage", 3, n_a)):
-            # a tensor divisor: torch divides by a Python scalar on the device as a product with its reciprocal
-            out[name] = torch.where(bad, torch.full_like(c[:, col], float("nan")),
-                                    c[:, col] / torch.full_like(c[:, col], float(den)))
-        if radii:
-            out["radii_a"], out["radii_b"] = r2[:, :n_a], r2[:, n_a:]
+    return (torch.empty(P, 1 + S, **f64), torch.empty(P, 4, dtype=torch.int64, device=dev),
+            torch.empty(P, dtype=torch.int32, device=dev), torch.empty(P, n_a + n_b, **f64) if radii else None)
+
+
+def _quality_result(kid, counts, status, r2, n_a, n_b, k):
+    """the dict that device_quality and device_quality_stream return, from what their entries wrote"""
+    c = counts.to(torch.float64)
+    bad = counts[:, 0] < 0
+    out = {"kid": kid[:, 0], "kid_subsets": kid[:, 1:], "counts": counts, "status": status}
+    for name, col, den in (("precision", 0, n_b), ("recall", 1, n_a), ("density", 2, k * n_b), ("coverage", 3, n_a)):
+        # a tensor divisor: torch divides by a Python scalar on the device as a product with its reciprocal
+        out[name] = torch.where(bad, torch.full_like(c[:, col], float("nan")),
+                                c[:, col] / torch.full_like(c[:, col], float(den)))
+    if r2 is not None:
+        out["radii_a"], out["radii_b"] = r2[:, :n_a], r2[:, n_a:]
     return out
 
 
@@ -1401,10 +1414,7 @@ def _quality_stream_check(a, b, k, panel_rows):
             raise ValueError(f"{name} holds {t.shape[-2]} rows: the row-panel route of the device sample-quality scores "
                              f"takes 2 .. {QUALITY_STREAM_MAX_ROWS} per set")
     _batch_limits(P, a.shape[-1])
-    k_max = min(a.shape[-2], b.shape[-2]) - 1
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= min(k_max, QUALITY_STREAM_MAX_K):
-        raise ValueError(f"k={k!r} must be an integer in [1, min(n_a, n_b) - 1] = [1, {k_max}] and at most "
-                         f"{QUALITY_STREAM_MAX_K} on the row-panel route")
+    _k_check(k, min(a.shape[-2], b.shape[-2]), QUALITY_STREAM_MAX_K)
     if panel_rows is not None and (isinstance(panel_rows, bool) or not isinstance(panel_rows, (int, np.integer)) or
                                    not 64 <= panel_rows <= 4096 or panel_rows % 64):
         raise ValueError(f"panel_rows={panel_rows!r} must be None or a multiple of 64 in [64, 4096]")
@@ -1433,46 +1443,15 @@ def device_quality_stream(a, b, k=5, radii=False, panel_rows=None, events=None, 
     not matter."""
     a, b, P = _quality_stream_check(a, b, k, panel_rows)
     n_a, n_b, D = a.shape[-2], b.shape[-2], a.shape[-1]
-    if events is not None and len(events) != QUALITY_STREAM_EVENTS:
-        raise ValueError(f"events must be {QUALITY_STREAM_EVENTS} torch.cuda.Event")
-    _require_cuda(a, "a")
-    _require_cuda(b, "b")
-    if a.device != b.device:
-        raise ValueError(f"a is on {a.device}, b on {b.device}")
-    lib = _hip.load()
-    (a, a_ps, a_rs), (b, b_ps, b_rs) = _fid_rows(a), _fid_rows(b)
-    dev = a.device
-    f64 = dict(dtype=torch.float64, device=dev)
-    kid = torch.empty(P, **f64)
-    counts = torch.empty(P, 4, dtype=torch.int64, device=dev)
-    status = torch.empty(P, dtype=torch.int32, device=dev)
-    r2 = torch.empty(P, n_a + n_b, **f64) if radii else None
-    rows = int(panel_rows) if panel_rows is not None else quality_stream_panel_rows(lib, P, n_a, n_b, D)
-    ws_bytes = lib.dt_quality_stream_workspace_bytes(P, n_a, n_b, D, rows)
-    if ws_bytes == 0:
-        raise ValueError(f"dt_quality_stream_workspace_bytes rejects P={P}, n_a={n_a}, n_b={n_b}, D={D}, "
-                         f"panel_rows={rows}")
-    with torch.cuda.device(dev):
-        ev = _stage_events(events)
-        ws = workspace
-        if ws is None:
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        elif ws.dtype != torch.uint8 or ws.device != dev or not ws.is_contiguous() or ws.numel() < ws_bytes:
-            raise ValueError(f"workspace must be a contiguous uint8 tensor of >= {ws_bytes} bytes on {dev}")
-        check(lib.dt_quality_stream_scores(ptr(a), n_a, a_ps, a_rs, ptr(b), n_b, b_ps, b_rs, P, D, int(k), rows, ptr(kid),
-                                           ptr(counts), ptr(r2), ptr(status), ptr(ws), ws_bytes, ev, stream_ptr()),
-              "dt_quality_stream_scores")
-        c = counts.to(torch.float64)
-        bad = counts[:, 0] < 0
-        out = {"kid": kid, "kid_subsets": torch.empty(P, 0, **f64), "counts": counts, "status": status}
-        for name, col, den in (("precision", 0, n_b), ("recall", 1, n_a), ("density", 2, int(k) * n_b),
-                               ("coverage", 3, n_a)):
-            # a tensor divisor, as in device_quality
-            out[name] = torch.where(bad, torch.full_like(c[:, col], float("nan")),
-                                    c[:, col] / torch.full_like(c[:, col], float(den)))
-        if radii:
-            out["radii_a"], out["radii_b"] = r2[:, :n_a], r2[:, n_a:]
-    return out
+
+    def call(c):
+        kid, counts, status, r2 = _quality_outputs(P, 0, n_a, n_b, radii, c.dev)
+        check(c.lib.dt_quality_stream_scores(*c.rows, int(k), c.panel_rows, ptr(kid), ptr(counts), ptr(r2), ptr(status),
+                                             *c.tail), "dt_quality_stream_scores")
+        return _quality_result(kid, counts, status, r2, n_a, n_b, int(k))
+    return _set_pair_call(
+        a, b, P, events, workspace, QUALITY_STREAM_EVENTS, "dt_quality_stream_workspace_bytes", call,
+        lambda lib: int(panel_rows) if panel_rows is not None else quality_stream_panel_rows(lib, P, n_a, n_b, D))
 
 
 def quality_route(n_a, n_b, k):
