@@ -65,6 +65,7 @@ import torch.nn.functional as F
 
 from distillation_trajectories_amd import _hip, engine
 from distillation_trajectories_amd._hip import COND_NONE, COND_ONE, COND_ZERO, HipLibraryError, check, ptr, stream_ptr
+from fused_readout import transparent    # block j as an exact selection of its input (tests/fused_readout.py)
 from oracle import unet_ref
 
 pytestmark = pytest.mark.gpu
@@ -508,22 +509,6 @@ POOL_SHAPES = (
     Case("P_sf0.3_32x32_B3", 0.3, 32, 32, 3, 2, 0, 1, 0, 23),    # 38 / 76 channels; 32 px: maxpool_kernel; then 16 .. 4 px
 )
 POOL_PATHS = ("tile epilogue", "slab sum", "maxpool_kernel")
-
-
-def transparent(sd32, j):
-    """the weights with block j made transparent: norm2's weight and bias zero, so relu(bn2(conv2)) is exactly 0 and the block
-    output is its skip path alone -- the input itself (identity skips), or, where the block has a 1x1 residual_conv, output
-    channel n = input channel n % cin through a 0 / 1 selection with zero bias"""
-    sd, name = dict(sd32), engine.BLOCK_NAMES[j]
-    for key in (f"{name}.norm2.weight", f"{name}.norm2.bias"):
-        sd[key] = torch.zeros_like(sd[key])
-    if f"{name}.residual_conv.weight" in sd:
-        w = torch.zeros_like(sd[f"{name}.residual_conv.weight"])
-        cout, cin = w.shape[:2]
-        w[torch.arange(cout), torch.arange(cout) % cin, 0, 0] = 1.0
-        sd[f"{name}.residual_conv.weight"] = w
-        sd[f"{name}.residual_conv.bias"] = torch.zeros_like(sd[f"{name}.residual_conv.bias"])
-    return sd
 
 
 def pool_path(c, j, splits):

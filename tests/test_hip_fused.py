@@ -5,6 +5,9 @@ the properties the reference's seeded workflow relies on (row independence, run-
 The reference vectors themselves (tests/golden: forwards, generate_trajectory, p_sample_loop, TrajectoryManager,
 compare_trajectories -- almost all on size factors 0.01 and 0.2) run through this kernel by default and through the layered
 kernels via the ``conv_path`` fixture of tests/test_hip_parity.py.  Tolerances: rtol 1e-4 (+ small atol) as there.
+
+These are end-to-end comparisons of eps.  The kernel's arithmetic is pinned in tests/test_hip_fused_blocks.py: every block on
+its own against float64, to within 4 x the fp32 rounding error of the CPU oracle and of the layered kernels.
 """
 import copy
 

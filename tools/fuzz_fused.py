@@ -1,9 +1,14 @@
 """Randomised parity of the fused small-model kernel: size factors with padded dims 16/32, 32/48, 32/64 (odd real channel counts),
 1-3 image channels, batches 1..40, the three update rules, plain / CFG / mixed batches, 1..80 timesteps (loops past 64 steps
 chain launches) -- the fused loop against the layered per-timestep launches, and single forwards against the oracle.
-Usage: fuzz_fused.py [cases] [seed]"""
+With [block draws] > 0, that many further random models are checked block by block against float64 (tests/fused_readout.py,
+the criterion of tests/test_hip_fused_blocks.py): a random block j, every readout model M(j, k), a random one-pass batch with a
+(t, condition mode) of its own per row -- the fused kernel's error within 4 x the larger of the fp32 CPU oracle's and the
+layered fp32 kernels'.
+Usage: fuzz_fused.py [cases] [seed] [block draws]"""
 import os, sys
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 import numpy as np
 import torch
 from distillation_trajectories_amd import engine
@@ -15,6 +20,7 @@ from oracle import unet_ref
 
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 40
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
+n_block_draws = int(sys.argv[3]) if len(sys.argv) > 3 else 0
 dev = "cuda:0"
 worst_f = worst_l = 0.0
 for case in range(n_cases):
@@ -80,3 +86,25 @@ for case in range(n_cases):
           f"loop fused vs layered {el:.1e}{'' if ok else '   <-- FAIL'}", flush=True)
     assert ok
 print("worst forward", worst_f, "worst loop", worst_l)
+
+if n_block_draws:
+    sys.path.insert(1, os.path.join(ROOT, "tests"))      # the readout helper lives beside the tests that share it
+    import fused_readout as fr
+    torch.set_num_threads(max(1, min(torch.get_num_threads(), 16)))
+for draw in range(n_block_draws):
+    sf = float(rng.choice([0.01, 0.08, 0.13, 0.15, 0.17, 0.2, 0.22, 0.25]))
+    C = int(rng.choice([1, 2, 3, 3, 3]))
+    cfg = Config(); cfg.image_size, cfg.channels = 16, C
+    sd32 = {k: v.clone().float() for k, v in make_model(DiffusionUNet, cfg, sf, seed=3000 + draw).state_dict().items() if v.dtype.is_floating_point}
+    j, B = int(rng.integers(-1, 8)), int(rng.integers(1, 7))
+    conds = tuple((int(rng.integers(0, 50)), int(rng.choice([COND_NONE, COND_ZERO, COND_ONE]))) for _ in range(B))
+    lay = fr.Layout("one_pass", B, 1, 0, 1, conds)
+    inp = fr.make_inputs(sd32, lay, torch.randn(B, C, 16, 16))
+    m = fr.measure_block(sd32, j, [lay], {lay.name: inp}, dev)[lay.name]
+    ok = fr.within_margin(m.fused, [m.layered, m.cpu]) and (j < 0 or fr.within_margin(m.cross, [m.layered, m.cpu]))
+    dims = (sd32["enc1.conv2.weight"].shape[0], sd32["enc2.conv2.weight"].shape[0])
+    print(f"block draw {draw}: sf={sf:4.2f} dims={dims} C={C} B={B} j={j:2d} K={len(m.models):2d}: [rel L2, max-abs] {m.line()}"
+          f"{'' if ok else '   <-- FAIL'}", flush=True)
+    assert ok
+if n_block_draws:
+    print("block draws ok", n_block_draws)
