@@ -16,6 +16,7 @@
 #include <new>
 #include <vector>
 
+#include "dt_batch.h"
 #include "dt_fused.h"
 #include "../../include/dt_hip_edit.h"
 #include "dt_internal.h"
@@ -101,21 +102,6 @@ struct BlockW {
   int tb_off;             // channel offset of this block in a time-bias row
 };
 
-// One forward shape, the key of every launch plan: Bt batch rows of H x W pictures made of imgs images -- every image once
-// (pass 0), then the images from `single` on a second time (pass 1), or all of them Bt / imgs times when single == 0.  The
-// split is part of the key because enc1's launches run over the images, not the rows.
-struct FwdShape {
-  int Bt, H, W, imgs, single;
-  static FwdShape rows_only(int Bt, int H, int W) { return FwdShape{Bt, H, W, Bt, 0}; }   // for what the split does not change (the workspace layout)
-  bool operator==(const FwdShape &o) const { return Bt == o.Bt && H == o.H && W == o.W && imgs == o.imgs && single == o.single; }
-  // DT_OK, DT_E_SHAPE (rows, images or picture size the kernels do not run) or DT_E_ARG (rows and images that do not fit together)
-  int validate() const {
-    if (Bt < 1 || imgs < 1 || H < 16 || W < 16 || H % 16 || W % 16) return DT_E_SHAPE;
-    if (single < 0 || single >= imgs || (single ? Bt != 2 * imgs - single : Bt % imgs != 0)) return DT_E_ARG;
-    return DT_OK;
-  }
-};
-
 // (tile, split) choice of the three conv slots (0 = 1x1 skip, 1 = conv1, 2 = conv2) of every block for
 // one forward shape, filled in by dt_unet_autotune; absent shapes use heuristic_choice
 struct TunedShape {
@@ -171,7 +157,7 @@ struct Bump {
 };
 
 bool use_fused(const dt_unet *u, int H, int W);
-void fused_common(const dt_unet *u, FusedArgs &a, int B, int n_pass, int B_single, const float *tb, int tb_div);
+void fused_common(const dt_unet *u, FusedArgs &a, const BatchSplit &b, const float *tb);
 
 // activation buffers of one forward, as float offsets into the workspace
 struct Plan {
@@ -350,21 +336,18 @@ int run_block(const dt_unet *u, const ResolvedForward &f, int j, const float *in
   return DT_OK;
 }
 
-// B images; the first B_single of them take one pass, the others n_pass (B_single > 0 needs n_pass == 2): rows
-// [pass 0 of all B images | pass 1 of images B_single .. B-1]
-int forward_impl(const dt_unet *u, const float *x, int B, int n_pass, int H, int W, const float *tb, int tb_div,
-                 float *eps, float *ws, size_t ws_bytes, hipStream_t s, int B_single = 0) {
-  if (!u || !x || !tb || !ws) return DT_E_NULL;
-  if (n_pass < 1 || tb_div < 1) return DT_E_SHAPE;
-  const int Bt = B * n_pass - B_single * (n_pass - 1);
-  const FwdShape sh{Bt, H, W, B, B_single};
-  if (const int bad = sh.validate()) return bad;
+// One forward of the batch b (dt_batch.h), which the caller has checked: forward_status, forward_mixed_status or loop_status.
+// eps == nullptr: the forward stops at the low-resolution head output.
+int forward_impl(const dt_unet *u, const float *x, const BatchSplit &b, int H, int W, const float *tb, float *eps, float *ws,
+                 size_t ws_bytes, hipStream_t s) {
+  const FwdShape sh = b.shape(H, W);
+  const int Bt = sh.Bt, tb_div = b.tb_div;
   const Plan pl = make_plan(u, sh);
   if (pl.total * sizeof(float) > ws_bytes) return DT_E_WORKSPACE;
   if (use_fused(u, H, W) && eps) {           // small model: the whole forward is one launch (dt_fused.hip)
     if (Bt % tb_div) return DT_E_ARG;
     FusedArgs a{};
-    fused_common(u, a, B, n_pass, B_single, tb, tb_div);
+    fused_common(u, a, b, tb);
     a.mode = FUSED_FORWARD; a.x = x; a.eps = eps;
     return launch_unet_fused(a, s);
   }
@@ -474,14 +457,14 @@ int build_fused(dt_unet *u, const float *const *bt, hipStream_t s) {
 // (head fusion off = the test hook that materialises every block output in the workspace: only the layered path has those)
 bool use_fused(const dt_unet *u, int H, int W) { return u->fused_ok && u->fused_on && u->head_fusion && H == 16 && W == 16; }
 
-void fused_common(const dt_unet *u, FusedArgs &a, int B, int n_pass, int B_single, const float *tb, int tb_div) {
+void fused_common(const dt_unet *u, FusedArgs &a, const BatchSplit &b, const float *tb) {
   a.ops = u->fused_ops_dev; a.n_ops = u->fused_n_ops; a.fbase = u->fused_slab; a.par = u->fused_par; a.n_par = u->fused_n_par;
   a.head_w = u->final_w; a.head_b = u->final_b;
-  a.tb = tb; a.tb_stride = u->tb_stride; a.tb_div = tb_div;
+  a.tb = tb; a.tb_stride = u->tb_stride; a.tb_div = b.tb_div;
   a.lds = u->fused_lds; a.G = u->fused_G;
   a.C = u->desc.channels; a.c0 = u->desc.dims[0]; a.c0p = u->cp[0];
-  a.B = B; a.n_pass = n_pass; a.B_single = B_single;
-  a.tb_rows = (B * n_pass - B_single * (n_pass - 1)) / tb_div;
+  a.B = b.B; a.n_pass = b.n_pass; a.B_single = b.B_single;
+  a.tb_rows = b.tb_rows();
   a.flops_per_row = fused_flops_per_row(a.C, u->desc.dims[0], u->desc.dims[1]);
 }
 
@@ -684,8 +667,9 @@ size_t dt_unet_workspace_bytes(const dt_unet *h, int batch_total, int H, int W) 
 
 int dt_unet_forward(const dt_unet *h, const float *x, int B, int n_pass, int H, int W, const float *tb, int tb_div,
                     float *eps, void *ws, size_t ws_bytes, void *stream) {
-  if (!eps) return DT_E_NULL;
-  return forward_impl(h, x, B, n_pass, H, W, tb, tb_div, eps, (float *)ws, ws_bytes, (hipStream_t)stream);
+  const BatchSplit b{B, n_pass, 0, tb_div};
+  if (const int bad = forward_status(h, x, b, H, W, tb, eps, ws)) return bad;
+  return forward_impl(h, x, b, H, W, tb, eps, (float *)ws, ws_bytes, (hipStream_t)stream);
 }
 
 // launches are timed on an otherwise idle GPU, where extra workgroups are free, whereas in the sampler other streams fill idle
@@ -893,41 +877,53 @@ int dt_unet_debug_activation(const dt_unet *h, int batch_total, int H, int W, in
   return DT_OK;
 }
 
-// One sampler call.  tb_div rows of a step's forward share one time-bias row; B_single: see forward_impl.
+// One sampler call: the record every entry below fills by name, the loop runs and the graph replay keys.
 struct SampleArgs {
-  int rule, B, n_pass, B_single, H, W, n_steps;
-  const float *tb;
-  int tb_div;
-  const float *coef;
-  const int32_t *has_noise;
-  const float *z;
-  const int32_t *z_row;
-  const int64_t *z_shift;
-  const float *w;
-  float w_scalar;
-  float *traj;
-  void *ws;
-  size_t ws_bytes;
-  hipStream_t s;
+  int rule = 0;
+  BatchSplit b{};
+  int H = 0, W = 0, n_steps = 0;
+  const float *tb = nullptr;
+  const float *coef = nullptr;            // host, [n_steps][4]
+  const int32_t *has_noise = nullptr;     // host, [n_steps]
+  const float *z = nullptr;
+  const int32_t *z_row = nullptr;
+  const int64_t *z_shift = nullptr;       // host, [n_steps] or null
+  const float *w = nullptr;
+  float w_scalar = 1.f;
+  float *traj = nullptr;
+  void *ws = nullptr;
+  size_t ws_bytes = 0;
+  hipStream_t s = nullptr;
   MaskArgs mk{};      // the masked entry only (dt_sample_trajectory_masked): known-region blend after every update
+
+  // every field by value, the three host arrays by content: two calls with equal keys issue the same launches
+  std::vector<unsigned char> key() const {
+    static_assert(sizeof(SampleArgs) == 160, "a field was added or removed: serialise it below, then correct this size");
+    std::vector<unsigned char> k;
+    auto put = [&k](const void *p, size_t n) { const unsigned char *c = (const unsigned char *)p; k.insert(k.end(), c, c + n); };
+    const int ints[9] = {rule, b.B, b.n_pass, b.B_single, b.tb_div, H, W, n_steps, z_shift ? 1 : 0};
+    const void *ptrs[11] = {tb, z, z_row, w, traj, ws, (const void *)s, mk.mask, mk.mask_row, mk.known, mk.known_row};
+    put(ints, sizeof(ints)); put(ptrs, sizeof(ptrs)); put(&w_scalar, sizeof(w_scalar)); put(&ws_bytes, sizeof(ws_bytes));
+    put(coef, sizeof(float) * 4 * n_steps); put(has_noise, sizeof(int32_t) * n_steps);
+    if (z_shift) put(z_shift, sizeof(int64_t) * n_steps);
+    return k;
+  }
 };
 
+// the loop over a batch the entry has checked (loop_status, dt_batch.h)
 static int sample_loop(const dt_unet *h, const SampleArgs &a) {
-  const int B = a.B, H = a.H, W = a.W;
+  const int B = a.b.B, H = a.H, W = a.W;
   const int E = h->desc.channels * H * W;
   const size_t slot = (size_t)B * E;
-  const FwdShape sh{B * a.n_pass - a.B_single * (a.n_pass - 1), H, W, B, a.B_single};
-  if (const int bad = sh.validate()) return bad;
-  if (a.tb_div < 1 || sh.Bt % a.tb_div) return DT_E_ARG;
-  const int tb_rows = sh.Bt / a.tb_div;         // time-bias rows per step
-  const Plan pl = make_plan(h, sh);
+  const int tb_rows = a.b.tb_rows();            // time-bias rows per step
+  const Plan pl = make_plan(h, a.b.shape(H, W));
   if (pl.total * sizeof(float) > a.ws_bytes) return DT_E_WORKSPACE;
   if (use_fused(h, H, W)) {
     // small model: forward + CFG mix + update of up to kFusedMaxSteps timesteps per launch, images resident in LDS
     for (int i0 = 0; i0 < a.n_steps; i0 += kFusedMaxSteps) {
       const int n = a.n_steps - i0 < kFusedMaxSteps ? a.n_steps - i0 : kFusedMaxSteps;
       FusedArgs fa{};
-      fused_common(h, fa, B, a.n_pass, a.B_single, a.tb + (size_t)i0 * tb_rows * h->tb_stride, a.tb_div);
+      fused_common(h, fa, a.b, a.tb + (size_t)i0 * tb_rows * h->tb_stride);
       fa.mode = FUSED_LOOP; fa.rule = a.rule; fa.n_steps = n;
       fa.traj = a.traj + (size_t)i0 * slot; fa.z = a.z; fa.z_row = a.z_row; fa.wg = a.w; fa.w_scalar = a.w_scalar;
       fa.mk = a.mk;                                  // (travels with every launch of a loop longer than kFusedMaxSteps)
@@ -948,14 +944,13 @@ static int sample_loop(const dt_unet *h, const SampleArgs &a) {
     float *xn = a.traj + (size_t)(i + 1) * slot;
     const bool dead = a.rule == DT_RULE_ENGINE && !a.has_noise[i];   // t == 0: the prediction is never used
     if (!dead) {      // the forward stops at the low-resolution head output; the update interpolates it (no eps tensor)
-      int st = forward_impl(h, x, B, a.n_pass, H, W, a.tb + (size_t)i * tb_rows * h->tb_stride, a.tb_div, nullptr, (float *)a.ws, a.ws_bytes,
-                            a.s, a.B_single);
+      int st = forward_impl(h, x, a.b, H, W, a.tb + (size_t)i * tb_rows * h->tb_stride, nullptr, (float *)a.ws, a.ws_bytes, a.s);
       if (st) return st;
     }
     // second-pass rows start at row B and belong to images B_single .. B-1: indexed by image through a pointer shifted back
-    int st = launch_cfg_update_lowres(a.rule, x, lowres, a.n_pass == 2 ? lowres + (size_t)(B - a.B_single) * (H / 2) * (W / 2) * 4 : nullptr, a.z,
+    int st = launch_cfg_update_lowres(a.rule, x, lowres, a.b.n_pass == 2 ? lowres + (size_t)(B - a.b.B_single) * (H / 2) * (W / 2) * 4 : nullptr, a.z,
                                       a.z_row, a.z_shift ? (long long)a.z_shift[i] : 0, a.coef + 4 * i, a.has_noise[i], a.w, a.w_scalar, xn,
-                                      B, h->desc.channels, H, W, a.B_single, a.s, a.mk);
+                                      B, h->desc.channels, H, W, a.b.B_single, a.s, a.mk);
     if (st) return st;
   }
   return DT_OK;
@@ -965,58 +960,60 @@ static int sample_loop(const dt_unet *h, const SampleArgs &a) {
  * repeated call (same buffers, same schedule) can replay an instantiated hipGraph instead of re-issuing each launch.
  * Opt-in with DT_GRAPH=1: measured on MI355X / ROCm 7.2 the replay is time-neutral (batch 8: 31.5 vs 31.5 ms per
  * 100 forwards, batch 256: 94.9 vs 94.9 ms/step) -- the loop is bound by the GPU-side latency of its dependent
- * kernels (~6 us each at batch 8), not by host launch cost, which the host threads already hide. */
-int dt_sample_trajectory(const dt_unet *h, int rule, int B, int n_pass, int H, int W, int n_steps, const float *tb,
-                         const float *coef, const int32_t *has_noise, const float *z, const int32_t *z_row,
-                         const int64_t *z_shift, const float *w, float w_scalar, float *traj, void *ws, size_t ws_bytes,
-                         void *stream) {
-  if (!h || !tb || !coef || !has_noise || !traj || !ws) return DT_E_NULL;
-  if (n_pass < 1 || n_pass > 2 || n_steps < 0 || rule < 0 || rule > DT_RULE_MANAGER) return DT_E_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  const SampleArgs a{rule, B, n_pass, 0, H, W, n_steps, tb, B, coef, has_noise, z, z_row, z_shift, w, w_scalar, traj, ws, ws_bytes, s};
+ * kernels (~6 us each at batch 8), not by host launch cost, which the host threads already hide.
+ * Reached from dt_sample_trajectory only; the key (SampleArgs::key) nevertheless covers the whole record. */
+static int run_or_replay(const dt_unet *h, const SampleArgs &a) {
   const char *genv = getenv("DT_GRAPH");
   const bool use_graph = genv && atoi(genv) != 0;
-  if (!use_graph || g_prof.on.load() || n_steps < 4) return sample_loop(h, a);
-  // ---- key: every argument by value (the small host arrays by content)
-  std::vector<unsigned char> key;
-  auto put = [&key](const void *p, size_t n) { const unsigned char *c = (const unsigned char *)p; key.insert(key.end(), c, c + n); };
-  const int ints[7] = {a.rule, a.B, a.n_pass, a.H, a.W, a.n_steps, a.z_shift ? 1 : 0};
-  const void *ptrs[7] = {a.tb, a.z, a.z_row, a.w, a.traj, a.ws, (const void *)a.s};
-  put(ints, sizeof(ints)); put(ptrs, sizeof(ptrs)); put(&a.w_scalar, sizeof(a.w_scalar)); put(&a.ws_bytes, sizeof(a.ws_bytes));
-  put(a.coef, sizeof(float) * 4 * n_steps); put(a.has_noise, sizeof(int32_t) * n_steps);
-  if (a.z_shift) put(a.z_shift, sizeof(int64_t) * n_steps);
-  const dt_unet *hm = h;
-  std::lock_guard<std::mutex> lock(hm->graph_mu);
-  for (const LoopGraph &g : hm->graphs)
-    if (g.key == key) return (int)hipGraphLaunch(g.exec, s);
+  if (!use_graph || g_prof.on.load() || a.n_steps < 4) return sample_loop(h, a);
+  std::vector<unsigned char> key = a.key();
+  std::lock_guard<std::mutex> lock(h->graph_mu);
+  for (const LoopGraph &g : h->graphs)
+    if (g.key == key) return (int)hipGraphLaunch(g.exec, a.s);
   // ---- first call with these arguments: capture the loop, instantiate, keep (at most 8 per handle)
-  hipError_t e = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
+  hipError_t e = hipStreamBeginCapture(a.s, hipStreamCaptureModeThreadLocal);
   if (e != hipSuccess) {   // stream cannot be captured (e.g. the legacy default stream): plain launches
     (void)hipGetLastError();
     return sample_loop(h, a);
   }
   const int st = sample_loop(h, a);
   LoopGraph g{};
-  e = hipStreamEndCapture(s, &g.graph);
+  e = hipStreamEndCapture(a.s, &g.graph);
   if (st != DT_OK) { if (e == hipSuccess && g.graph) (void)hipGraphDestroy(g.graph); return st; }
   if (e != hipSuccess) return (int)e;
   e = hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0);
   if (e != hipSuccess) { (void)hipGraphDestroy(g.graph); return (int)e; }
   g.key = std::move(key);
-  if (hm->graphs.size() >= 8) { (void)hipGraphExecDestroy(hm->graphs.front().exec); (void)hipGraphDestroy(hm->graphs.front().graph); hm->graphs.erase(hm->graphs.begin()); }
-  hm->graphs.push_back(std::move(g));
-  if (getenv("DT_GRAPH_DEBUG")) fprintf(stderr, "[dt_hip] captured sampler loop: %d steps, batch %d -> graph #%zu\n", n_steps, B, hm->graphs.size());
-  return (int)hipGraphLaunch(hm->graphs.back().exec, s);
+  if (h->graphs.size() >= 8) { (void)hipGraphExecDestroy(h->graphs.front().exec); (void)hipGraphDestroy(h->graphs.front().graph); h->graphs.erase(h->graphs.begin()); }
+  h->graphs.push_back(std::move(g));
+  if (getenv("DT_GRAPH_DEBUG")) fprintf(stderr, "[dt_hip] captured sampler loop: %d steps, batch %d -> graph #%zu\n", a.n_steps, a.b.B, h->graphs.size());
+  return (int)hipGraphLaunch(h->graphs.back().exec, a.s);
+}
+
+// what every sampler entry is given, by name (the batch, w_scalar and the mask are the entry's own)
+#define DT_LOOP_ARGS(a)                                                                                                  \
+  SampleArgs a;                                                                                                          \
+  a.rule = rule; a.H = H; a.W = W; a.n_steps = n_steps; a.tb = tb; a.coef = coef; a.has_noise = has_noise; a.z = z;     \
+  a.z_row = z_row; a.z_shift = z_shift; a.w = w; a.traj = traj; a.ws = ws; a.ws_bytes = ws_bytes; a.s = (hipStream_t)stream
+
+int dt_sample_trajectory(const dt_unet *h, int rule, int B, int n_pass, int H, int W, int n_steps, const float *tb,
+                         const float *coef, const int32_t *has_noise, const float *z, const int32_t *z_row,
+                         const int64_t *z_shift, const float *w, float w_scalar, float *traj, void *ws, size_t ws_bytes,
+                         void *stream) {
+  DT_LOOP_ARGS(a);
+  a.b = BatchSplit{B, n_pass, 0, B};           // one time-bias row per pass
+  a.w_scalar = w_scalar;
+  if (const int bad = sample_status(h, rule, a.b, H, W, n_steps, tb, coef, has_noise, traj, ws)) return bad;
+  return run_or_replay(h, a);
 }
 
 int dt_sample_trajectory_mixed(const dt_unet *h, int rule, int B, int B_single, int H, int W, int n_steps, const float *tb,
                                int tb_div, const float *coef, const int32_t *has_noise, const float *z, const int32_t *z_row,
                                const int64_t *z_shift, const float *w, float *traj, void *ws, size_t ws_bytes, void *stream) {
-  if (!h || !tb || !coef || !has_noise || !traj || !ws || !w) return DT_E_NULL;
-  if (n_steps < 0 || rule < 0 || rule > DT_RULE_MANAGER || B < 2 || B_single < 1 || B_single >= B || tb_div < 1) return DT_E_ARG;
-  if ((2 * B - B_single) % tb_div || B_single % tb_div || !h->share_enc1) return DT_E_ARG;   // a time-bias row never straddles the single / CFG boundary
-  return sample_loop(h, SampleArgs{rule, B, 2, B_single, H, W, n_steps, tb, tb_div, coef, has_noise, z, z_row, z_shift, w, 1.f, traj, ws, ws_bytes,
-                                   (hipStream_t)stream});
+  DT_LOOP_ARGS(a);
+  a.b = BatchSplit{B, 2, B_single, tb_div};     // (w_scalar stays 1: the guidance weights are per image)
+  if (const int bad = sample_mixed_status(h, rule, a.b, H, W, n_steps, tb, coef, has_noise, w, traj, ws, h && h->share_enc1)) return bad;
+  return sample_loop(h, a);
 }
 
 // The masked loop of the editing stage (include/dt_hip_edit.h).  Always plain launches: it takes no part in the opt-in graph replay.
@@ -1025,26 +1022,21 @@ int dt_sample_trajectory_masked(const dt_unet *h, int rule, int B, int n_pass, i
                                 const int32_t *z_row, const int64_t *z_shift, const float *w, float w_scalar, const float *mask,
                                 const int32_t *mask_row, const float *known, const int32_t *known_row, float *traj, void *ws,
                                 size_t ws_bytes, void *stream) {
-  if (!h || !tb || !coef || !has_noise || !traj || !ws || !mask || !known) return DT_E_NULL;
-  if (n_pass < 1 || n_pass > 2 || n_steps < 0 || rule < 0 || rule > DT_RULE_MANAGER || tb_div < 1) return DT_E_ARG;
-  if (B < 1 || B_single < 0 || B_single > B || (n_pass == 1 && B_single)) return DT_E_ARG;
-  if (B_single == B) { n_pass = 1; B_single = 0; }                       // every image takes one pass
-  if (B_single) {                                                        // a mixed batch: dt_sample_trajectory_mixed's conditions
-    if (!w) return DT_E_NULL;
-    if ((2 * B - B_single) % tb_div || B_single % tb_div || !h->share_enc1) return DT_E_ARG;
-  }
-  if (((uintptr_t)mask | (uintptr_t)known | (uintptr_t)traj) & 15) return DT_E_ARG;   // float4 reads of the layered update
-  SampleArgs a{rule, B, n_pass, B_single, H, W, n_steps, tb, tb_div, coef, has_noise, z, z_row, z_shift, w, w_scalar, traj, ws, ws_bytes,
-               (hipStream_t)stream};
+  DT_LOOP_ARGS(a);
+  a.b = BatchSplit{B, n_pass, B_single, tb_div};
+  a.w_scalar = w_scalar;
   a.mk = MaskArgs{mask, mask_row, known, known_row};
+  if (const int bad = sample_masked_status(h, rule, a.b, H, W, n_steps, tb, coef, has_noise, w, mask, known, traj, ws, h && h->share_enc1)) return bad;
+  a.b = a.b.normalised();                      // every image takes one pass: a one-pass batch
   return sample_loop(h, a);
 }
+#undef DT_LOOP_ARGS
 
 int dt_unet_forward_mixed(const dt_unet *h, const float *x, int B, int B_single, int H, int W, const float *tb, int tb_div,
                           float *eps, void *ws, size_t ws_bytes, void *stream) {
-  if (!eps || !h) return DT_E_NULL;
-  if (B_single < 1 || B_single >= B || tb_div < 1 || (2 * B - B_single) % tb_div || B_single % tb_div || !h->share_enc1) return DT_E_ARG;
-  return forward_impl(h, x, B, 2, H, W, tb, tb_div, eps, (float *)ws, ws_bytes, (hipStream_t)stream, B_single);
+  const BatchSplit b{B, 2, B_single, tb_div};
+  if (const int bad = forward_mixed_status(h, x, b, H, W, tb, eps, ws, h && h->share_enc1)) return bad;
+  return forward_impl(h, x, b, H, W, tb, eps, (float *)ws, ws_bytes, (hipStream_t)stream);
 }
 
 // an empty kernel with a recognisable name: lets an external profiler (rocprofv3 traces) bracket a region of the stream

@@ -12,8 +12,8 @@ staged as one table and uploaded once; there is no device RNG.
 import torch
 
 from .. import engine
-from .._hip import COND_NONE, COND_ONE, COND_ZERO, RULE_ENGINE
-from ..analysis.trajectory_engine import engine_coefficients_from_alphas
+from .._hip import RULE_ENGINE
+from ..analysis.trajectory_engine import _plan, engine_coefficients_from_alphas, uses_cfg
 
 
 def schedule(diffusion_params):
@@ -49,12 +49,11 @@ def reverse_loop(handle, traj, t_first, coefs, z, H, W, z_row=None, mask=None, k
     ``mask`` / ``known`` (and their row tables) the known-region blend follows every update.  ``guidance_scale`` > 1 (the
     sweeps only; the reference's editing loops have no guidance) takes trajectory_engine's two-pass CFG branch."""
     order = list(range(t_first, -1, -1))
-    if guidance_scale is not None and guidance_scale > 1.0:
-        tb = handle.time_bias([t for t in order for _ in (0, 1)], [COND_ZERO, COND_ONE] * len(order))
-        n_pass, w = 2, float(guidance_scale)
-    else:
-        tb, n_pass, w = handle.time_bias(order, [COND_NONE] * len(order)), 1, 1.0
-    args = dict(z=z if z is not None and z.numel() else None, z_row=z_row, z_shift=list(range(len(order))), w_scalar=w)
+    cfg = uses_cfg(guidance_scale)
+    t_rows, modes, n_pass = _plan(t_first + 1, cfg)
+    tb = handle.time_bias(t_rows, modes)
+    args = dict(z=z if z is not None and z.numel() else None, z_row=z_row, z_shift=list(range(len(order))),
+                w_scalar=float(guidance_scale) if cfg else 1.0)
     cs, noise = [coefs[t] for t in order], [t > 0 for t in order]
     if mask is None:
         return handle.sample(RULE_ENGINE, traj, H, W, tb, n_pass, cs, noise, **args)

@@ -5,6 +5,7 @@ host<->device copies only; all arithmetic on trajectories happens in csrc/ kerne
 Everything here raises if the HIP library is missing or a tensor is not on a CUDA(HIP)
 device -- the product has no CPU path (the CPU restatement lives in oracle/ and is test-only).
 """
+import collections
 import ctypes
 import math
 import os
@@ -122,6 +123,17 @@ def set_fused_default(on):
     _FUSED_DEFAULT = bool(on)
     for _, h in list(_HANDLES.values()):
         h.set_fused(_FUSED_DEFAULT)
+
+
+class _Split(collections.namedtuple("_Split", "B n_pass b_single tb_div mixed")):
+    """The batch of one forward or sampler call, as BatchSplit of csrc/dt_batch.h: B images of which the first ``b_single`` take
+    one pass and the others ``n_pass``; ``tb_div`` rows share a time-bias row.  ``mixed``: the call goes to the library's
+    mixed-batch entry (which refuses ``b_single`` == 0 and ``b_single`` == B) and not to the plain one."""
+    __slots__ = ()
+
+    @property
+    def rows(self):
+        return self.n_pass * self.B - self.b_single * (self.n_pass - 1)
 
 
 class UNetHandle:
@@ -374,58 +386,35 @@ class UNetHandle:
     def forward(self, x, tb, n_pass, tb_div, tune=None):
         """eps[n_pass*B,C,H,W] for x[B,C,H,W]; tb rows as documented in dt_hip.h."""
         _require_cuda(x, "x")
-        x = x.contiguous().float()
         B, C, H, W = x.shape
         if C != self.channels:
             raise HipLibraryError(f"x has {C} channels, the model expects {self.channels}")
-        eps = torch.empty(n_pass * B, C, H, W, dtype=torch.float32, device=self.device)
-        ws = self.workspace(n_pass * B, H, W)
-
-        def run():
-            with torch.cuda.device(self.device):
-                check(self.lib.dt_unet_forward(self.h, ptr(x), B, n_pass, H, W, ptr(tb), tb_div, ptr(eps), ptr(ws),
-                                               c_size_t(ws.numel()), stream_ptr()), "dt_unet_forward")
-        self.ensure_plan(n_pass * B, H, W, B, 0, tune, run)
-        run()
-        return eps
+        return self._forward(x, tb, _Split(B, n_pass, 0, tb_div, False), tune)
 
     def forward_mixed(self, x, tb, b_single, tb_div, tune=None):
         """eps[2B - b_single, C, H, W] of a mixed batch (dt_unet_forward_mixed): images [0, b_single) take one pass,
         the others two; rows [pass 0 of all images | pass 1 of images b_single..]; row r uses tb[r // tb_div]."""
         _require_cuda(x, "x")
+        return self._forward(x, tb, _Split(x.shape[0], 2, b_single, tb_div, True), tune)
+
+    def _forward(self, x, tb, split, tune=None):
+        """One forward of the batch ``split`` of x[B,C,H,W], through the entry the split names, under the shape's launch plan."""
         x = x.contiguous().float()
         B, C, H, W = x.shape
-        rows = 2 * B - b_single
+        rows = split.rows
         eps = torch.empty(rows, C, H, W, dtype=torch.float32, device=self.device)
         ws = self.workspace(rows, H, W)
+        tail = (H, W, ptr(tb), split.tb_div, ptr(eps), ptr(ws), c_size_t(ws.numel()))
 
         def run():
             with torch.cuda.device(self.device):
-                check(self.lib.dt_unet_forward_mixed(self.h, ptr(x), B, b_single, H, W, ptr(tb), tb_div, ptr(eps), ptr(ws),
-                                                     c_size_t(ws.numel()), stream_ptr()), "dt_unet_forward_mixed")
-        self.ensure_plan(rows, H, W, B, b_single, tune, run)
+                if split.mixed:
+                    check(self.lib.dt_unet_forward_mixed(self.h, ptr(x), B, split.b_single, *tail, stream_ptr()), "dt_unet_forward_mixed")
+                else:
+                    check(self.lib.dt_unet_forward(self.h, ptr(x), B, split.n_pass, *tail, stream_ptr()), "dt_unet_forward")
+        self.ensure_plan(rows, H, W, B, split.b_single, tune, run)
         run()
         return eps
-
-    def sample_mixed(self, rule, traj, H, W, tb, tb_div, b_single, coef, has_noise, z, z_row, z_shift, w):
-        """len(coef) reverse steps in place on traj[(n_steps+1), B, E] of a mixed batch (dt_sample_trajectory_mixed)."""
-        _require_cuda(traj, "traj")
-        n_steps = len(coef)
-        B = traj.shape[1]
-        rows = 2 * B - b_single
-        assert traj.shape[0] == n_steps + 1 and traj.is_contiguous() and traj.dtype == torch.float32
-        coef_c = (c_float * (4 * n_steps))(*[float(v) for row in coef for v in (list(row) + [0.0] * 4)[:4]])
-        noise_c = (c_int32 * n_steps)(*[int(bool(v)) for v in has_noise])
-        shift_c = (c_int64 * n_steps)(*[int(v) for v in (z_shift if z_shift is not None else [0] * n_steps)])
-        ws = self.workspace(rows, H, W)
-        if n_steps and self.shape(rows, H, W, B, b_single) not in self._plans:
-            per_step = rows // tb_div
-            self.forward_mixed(traj[0].reshape(B, self.channels, H, W), tb[:per_step].contiguous(), b_single, tb_div)
-        with torch.cuda.device(self.device):
-            check(self.lib.dt_sample_trajectory_mixed(self.h, rule, B, b_single, H, W, n_steps, ptr(tb), tb_div, coef_c, noise_c,
-                                                      ptr(z), ptr(z_row), shift_c, ptr(w), ptr(traj), ptr(ws),
-                                                      c_size_t(ws.numel()), stream_ptr()), "dt_sample_trajectory_mixed")
-        return traj
 
     def debug_activation(self, batch_total, H, W, which):
         """NHWC view [Bt,h,w,cp] of block ``which``'s output inside the workspace of the last forward."""
@@ -436,38 +425,15 @@ class UNetHandle:
         n = batch_total * oh.value * ow.value * cp.value
         return ws[off.value: off.value + n].view(batch_total, oh.value, ow.value, cp.value)
 
-    def sample(self, rule, traj, H, W, tb, n_pass, coef, has_noise, z=None, z_row=None, z_shift=None, w=None,
-               w_scalar=1.0):
-        """Run len(coef) reverse steps in place on traj[(n_steps+1), B, E] (slot 0 = x_T)."""
-        _require_cuda(traj, "traj")
+    def _sample(self, rule, traj, H, W, tb, split, coef, has_noise, z, z_row, z_shift, w, w_scalar, mask=None, known=None,
+                mask_row=None, known_row=None):
+        """len(coef) reverse steps in place on traj[(n_steps+1), B, E] of the batch ``split``: the masked entry when a mask is
+        given, else the entry the split names.  A shape that has no launch plan yet runs one forward first, which settles it."""
         n_steps = len(coef)
         B = traj.shape[1]
         assert traj.shape[0] == n_steps + 1 and traj.is_contiguous() and traj.dtype == torch.float32
-        coef_c = (c_float * (4 * n_steps))(*[float(v) for row in coef for v in (list(row) + [0.0] * 4)[:4]])
-        noise_c = (c_int32 * n_steps)(*[int(bool(v)) for v in has_noise])
-        shift_c = (c_int64 * n_steps)(*[int(v) for v in (z_shift if z_shift is not None else [0] * n_steps)])
-        ws = self.workspace(n_pass * B, H, W)
-        if n_steps and self.shape(n_pass * B, H, W, B, 0) not in self._plans:
-            self.forward(traj[0].reshape(B, self.channels, H, W), tb[:n_pass].contiguous(), n_pass, B)
-        with torch.cuda.device(self.device):
-            check(self.lib.dt_sample_trajectory(self.h, rule, B, n_pass, H, W, n_steps, ptr(tb), coef_c, noise_c,
-                                                ptr(z), ptr(z_row), shift_c, ptr(w), c_float(w_scalar), ptr(traj),
-                                                ptr(ws), c_size_t(ws.numel()), stream_ptr()),
-                  "dt_sample_trajectory")
-        return traj
-
-    def sample_masked(self, rule, traj, H, W, tb, n_pass, coef, has_noise, mask, known, mask_row=None, known_row=None, z=None,
-                      z_row=None, z_shift=None, w=None, w_scalar=1.0, b_single=0, tb_div=None):
-        """``sample`` (``b_single`` > 0: ``sample_mixed``) with the known-region blend after every update
-        (dt_sample_trajectory_masked): row b of traj keeps ``known[known_row[b]]`` where ``mask[mask_row[b]]`` is 0.  mask and
-        known are fp32 device tensors [rows, E]; a row table that is None is the identity."""
-        _require_cuda(traj, "traj"); _require_cuda(mask, "mask"); _require_cuda(known, "known")
-        n_steps = len(coef)
-        B, E = traj.shape[1], traj.shape[2]
-        rows = n_pass * B - b_single * (n_pass - 1)
-        tb_div = B if tb_div is None else tb_div
-        assert traj.shape[0] == n_steps + 1 and traj.is_contiguous() and traj.dtype == torch.float32
-        for name, t, row in (("mask", mask, mask_row), ("known", known, known_row)):
+        for name, t, row in (("mask", mask, mask_row), ("known", known, known_row)) if mask is not None else ():
+            E = traj.shape[2]
             if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != E:
                 raise HipLibraryError(f"sample_masked: {name} must be a contiguous float32 [rows, {E}] tensor, got {tuple(t.shape)} {t.dtype}")
             if row is None and t.shape[0] < B:
@@ -477,19 +443,47 @@ class UNetHandle:
         coef_c = (c_float * (4 * n_steps))(*[float(v) for row in coef for v in (list(row) + [0.0] * 4)[:4]])
         noise_c = (c_int32 * n_steps)(*[int(bool(v)) for v in has_noise])
         shift_c = (c_int64 * n_steps)(*[int(v) for v in (z_shift if z_shift is not None else [0] * n_steps)])
+        rows = split.rows
         ws = self.workspace(rows, H, W)
-        if n_steps and self.shape(rows, H, W, B, b_single) not in self._plans:
-            x0 = traj[0].reshape(B, self.channels, H, W)
-            if b_single:
-                self.forward_mixed(x0, tb[:rows // tb_div].contiguous(), b_single, tb_div)
-            else:
-                self.forward(x0, tb[:rows // tb_div].contiguous(), n_pass, tb_div)
+        if n_steps and self.shape(rows, H, W, B, split.b_single) not in self._plans:
+            self._forward(traj[0].reshape(B, self.channels, H, W), tb[:rows // split.tb_div].contiguous(),
+                          split._replace(n_pass=2) if split.mixed else split)
+        noise = (coef_c, noise_c, ptr(z), ptr(z_row), shift_c, ptr(w))
         with torch.cuda.device(self.device):
-            check(self.lib.dt_sample_trajectory_masked(self.h, rule, B, n_pass, b_single, H, W, n_steps, ptr(tb), tb_div, coef_c,
-                                                       noise_c, ptr(z), ptr(z_row), shift_c, ptr(w), c_float(w_scalar),
-                                                       ptr(mask), ptr(mask_row), ptr(known), ptr(known_row), ptr(traj), ptr(ws),
-                                                       c_size_t(ws.numel()), stream_ptr()), "dt_sample_trajectory_masked")
+            tail = (ptr(traj), ptr(ws), c_size_t(ws.numel()), stream_ptr())
+            if mask is not None:
+                check(self.lib.dt_sample_trajectory_masked(self.h, rule, B, split.n_pass, split.b_single, H, W, n_steps, ptr(tb), split.tb_div,
+                                                           *noise, c_float(w_scalar), ptr(mask), ptr(mask_row), ptr(known), ptr(known_row),
+                                                           *tail), "dt_sample_trajectory_masked")
+            elif split.mixed:
+                check(self.lib.dt_sample_trajectory_mixed(self.h, rule, B, split.b_single, H, W, n_steps, ptr(tb), split.tb_div, *noise, *tail),
+                      "dt_sample_trajectory_mixed")
+            else:
+                check(self.lib.dt_sample_trajectory(self.h, rule, B, split.n_pass, H, W, n_steps, ptr(tb), *noise, c_float(w_scalar), *tail),
+                      "dt_sample_trajectory")
         return traj
+
+    def sample(self, rule, traj, H, W, tb, n_pass, coef, has_noise, z=None, z_row=None, z_shift=None, w=None,
+               w_scalar=1.0):
+        """Run len(coef) reverse steps in place on traj[(n_steps+1), B, E] (slot 0 = x_T)."""
+        _require_cuda(traj, "traj")
+        B = traj.shape[1]
+        return self._sample(rule, traj, H, W, tb, _Split(B, n_pass, 0, B, False), coef, has_noise, z, z_row, z_shift, w, w_scalar)
+
+    def sample_mixed(self, rule, traj, H, W, tb, tb_div, b_single, coef, has_noise, z, z_row, z_shift, w):
+        """len(coef) reverse steps in place on traj[(n_steps+1), B, E] of a mixed batch (dt_sample_trajectory_mixed)."""
+        _require_cuda(traj, "traj")
+        return self._sample(rule, traj, H, W, tb, _Split(traj.shape[1], 2, b_single, tb_div, True), coef, has_noise, z, z_row, z_shift, w, 1.0)
+
+    def sample_masked(self, rule, traj, H, W, tb, n_pass, coef, has_noise, mask, known, mask_row=None, known_row=None, z=None,
+                      z_row=None, z_shift=None, w=None, w_scalar=1.0, b_single=0, tb_div=None):
+        """``sample`` (``b_single`` > 0: ``sample_mixed``) with the known-region blend after every update
+        (dt_sample_trajectory_masked): row b of traj keeps ``known[known_row[b]]`` where ``mask[mask_row[b]]`` is 0.  mask and
+        known are fp32 device tensors [rows, E]; a row table that is None is the identity."""
+        _require_cuda(traj, "traj"); _require_cuda(mask, "mask"); _require_cuda(known, "known")
+        B = traj.shape[1]
+        split = _Split(B, n_pass, b_single, B if tb_div is None else tb_div, bool(b_single))
+        return self._sample(rule, traj, H, W, tb, split, coef, has_noise, z, z_row, z_shift, w, w_scalar, mask, known, mask_row, known_row)
 
 
 def cfg_update_masked(rule, x, eps_u, eps_c, z, coef, has_noise, mask, known, mask_row=None, known_row=None, w=None,
