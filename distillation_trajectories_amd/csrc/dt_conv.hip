@@ -37,6 +37,7 @@ __global__ __launch_bounds__(256, 4) void conv_gemm_kernel(const ConvParams p) {
   const int half = lane >> 5, l31 = lane & 31;
   const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
   const int HW = p.H * p.W;
+  const ConvRowMath rm = kernarg_row_math();   // (not p.rm: see kernarg_params)
 
   // ---- per-thread staging coordinates (fixed for the whole K walk)
   int a_off[A_PER], a_off2[A_PER], a_y[A_PER], a_x[A_PER];
@@ -49,9 +50,9 @@ __global__ __launch_bounds__(256, 4) void conv_gemm_kernel(const ConvParams p) {
     const int m = m0 + row;
     a_ok[j] = m < p.M;
     const int mm = a_ok[j] ? m : 0;
-    const int b = mm / HW, rem = mm - b * HW;
-    a_y[j] = rem / p.W;
-    a_x[j] = rem - a_y[j] * p.W;
+    const RowPixel px = row_pixel(mm, HW, p.W, rm);
+    a_y[j] = px.y;
+    a_x[j] = px.x;
     a_off[j] = mm * p.cin_p + lslot * 4;       // M*cin_p < 2^31 is checked by the host
     a_off2[j] = mm * p.cin2_p + lslot * 4;     // fused skip walk (same pixel, other tensor)
     a_lds[j] = q * 4;
@@ -132,7 +133,7 @@ __global__ __launch_bounds__(256, 4) void conv_gemm_kernel(const ConvParams p) {
     __syncthreads();
   }
 
-  conv_epilogue<BM, BN, 1>(p, acc, lds, m0, n0, wm, wn, half, l31);
+  conv_epilogue<BM, BN, 1, false, true>(p, acc, lds, m0, n0, wm, wn, half, l31);
 }
 
 int launch_splitk_epilogue(const ConvParams &p, hipStream_t s);
@@ -140,8 +141,11 @@ int launch_splitk_epilogue(const ConvParams &p, hipStream_t s);
 #define DT_GEMM_ROW(cls, kind, bm, bn, kc, wk) {{kind, bm, bn, kc, wk, cls}, conv_gemm_kernel<bm, bn>},
 static const ConvKernel kGemmKernels[] = {DT_CONV_FORMS_FP32(DT_GEMM_ROW)};
 
-int launch_conv(const ConvParams &p, hipStream_t s) {
+int launch_conv(const ConvParams &p_in, hipStream_t s) {
+  ConvParams p = p_in;
   if (!p.in || !p.w || !p.scale || !p.shift || !p.out) return DT_E_NULL;
+  if (p.H < 1 || p.W < 1) return DT_E_SHAPE;
+  p.rm = make_row_math(p.H, p.W, p.m_per_tb, p.x3_imgs);   // every run-time divisor of the kernels' row arithmetic
   if (p.cin_p % 16 || p.cout_p % 16 || p.n_p % kNPad || p.M <= 0) return DT_E_SHAPE;
   if ((long long)p.M * p.cin_p >= (1ll << 31) || (long long)p.M * p.cout_p * (p.n_dup > 1 ? p.n_dup : 1) >= (1ll << 31)) return DT_E_SHAPE;
   if (const int st = conv_admissible(p)) return st;
@@ -243,7 +247,7 @@ __device__ inline float4 splitk_finish(const ConvParams &p, unsigned m, int n, s
   float4 v = make_float4(a.x * sc.x + sh.x, a.y * sc.y + sh.y, a.z * sc.z + sh.z, a.w * sc.w + sh.w);
   if (p.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
   if (p.tb) {
-    const float4 t = *reinterpret_cast<const float4 *>(p.tb + (size_t)(m / (unsigned)p.m_per_tb) * p.tb_stride + n);
+    const float4 t = *reinterpret_cast<const float4 *>(p.tb + (size_t)row_tb((int)m, p.rm) * p.tb_stride + n);
     v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w;
   }
   if (p.add) {
@@ -259,23 +263,20 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(const ConvParams p
   // 32-bit index math (launch_conv guarantees M * cout_p < 2^31)
   const unsigned c4 = (unsigned)p.cout_p >> 2;
   const size_t slab_stride = (size_t)p.M * p.cout_p;
+  const bool pow2 = (c4 & (c4 - 1)) == 0;
+  const int sh4 = 31 - __builtin_clz(c4);
   if (!POOL) {
     const unsigned total = (unsigned)p.M * c4;
-    const bool pow2 = (c4 & (c4 - 1)) == 0;
-    const int sh4 = 31 - __builtin_clz(c4);
     for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
       const unsigned m = pow2 ? i >> sh4 : i / c4;
       splitk_finish<S>(p, m, (int)(i - m * c4) * 4, slab_stride);
     }
   } else {
-    const unsigned Wo = (unsigned)p.W >> 1, Ho = (unsigned)p.H >> 1, HW = (unsigned)(p.H * p.W);
     const unsigned total = ((unsigned)p.M >> 2) * c4;                    // one thread per (2x2 window, channel quad)
     for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-      const unsigned wq = i / c4;
+      const unsigned wq = pow2 ? i >> sh4 : i / c4;
       const int n = (int)(i - wq * c4) * 4;
-      const unsigned xo = wq % Wo, r = wq / Wo;
-      const unsigned yo = r % Ho, b = r / Ho;
-      const unsigned m00 = b * HW + 2 * yo * (unsigned)p.W + 2 * xo;
+      const unsigned m00 = (unsigned)pool_first_row((int)wq, p.H, p.W, p.rm);
       const float4 a = splitk_finish<S>(p, m00, n, slab_stride), bq = splitk_finish<S>(p, m00 + 1, n, slab_stride);
       const float4 c = splitk_finish<S>(p, m00 + p.W, n, slab_stride), d = splitk_finish<S>(p, m00 + p.W + 1, n, slab_stride);
       float4 mx;

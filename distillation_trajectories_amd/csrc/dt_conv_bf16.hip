@@ -39,6 +39,7 @@ __global__ __launch_bounds__(256, BM * BN > 128 * 128 ? 2 : 3) void conv_gemm_bf
   const int half = lane >> 5, l31 = lane & 31;
   const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
   const int HW = p.H * p.W;
+  const ConvRowMath rm = kernarg_row_math();   // (not p.rm: see kernarg_params)
 
   // ---- A staging: item -> (row, k-half): 8 consecutive k = 32 contiguous bytes of one pixel; AP items per thread
   constexpr int NT = 64 * WM * WN;
@@ -52,8 +53,8 @@ __global__ __launch_bounds__(256, BM * BN > 128 * 128 ? 2 : 3) void conv_gemm_bf
     const int m = m0 + rowi;
     a_ok[i] = item < BM * 2 && m < p.M;
     const int mm = a_ok[i] ? m : 0;
-    const int b = mm / HW, rem = mm - b * HW;
-    a_y[i] = rem / p.W; a_x[i] = rem - a_y[i] * p.W;
+    const RowPixel px = row_pixel(mm, HW, p.W, rm);
+    a_y[i] = px.y; a_x[i] = px.x;
     a_off[i] = mm * p.cin_p + hh * 8;
     a_off2[i] = mm * p.cin2_p + hh * 8;                               // fused skip walk
     a_lds[i] = rowi * 16 + ((hh ^ ((rowi >> 3) & 1)) << 3);          // element offset inside a plane
@@ -163,7 +164,7 @@ __global__ __launch_bounds__(256, BM * BN > 128 * 128 ? 2 : 3) void conv_gemm_bf
     __syncthreads();
   }
   static_assert(2 * STAGE * sizeof(__bf16) >= F.stage_bytes(), "epilogue stage");
-  conv_epilogue<BM, BN, 1>(p, acc, reinterpret_cast<float *>(lds), m0, n0, wm, wn, half, l31);
+  conv_epilogue<BM, BN, 1, true>(p, acc, reinterpret_cast<float *>(lds), m0, n0, wm, wn, half, l31);
 }
 
 #define DT_BF16_ROW(cls, kind, bm, bn, kc, wk) {{kind, bm, bn, kc, wk, cls}, conv_gemm_bf16x6_kernel<bm, bn>},

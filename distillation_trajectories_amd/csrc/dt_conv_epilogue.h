@@ -42,6 +42,28 @@ __device__ inline void mfma_bf16x6(f32x16 &acc, const bf16x8 (&fa)[3], const bf1
   acc = c;
 }
 
+// The launch's arguments as the epilogue reads them: from the kernel-argument segment, when the epilogue starts.  Arguments
+// read through the kernel's by-value ConvParams are loaded at kernel entry and then occupy scalar registers through the
+// whole K walk, where the strip kernels have none to spare (they keep 50-110 scalars in VGPR lanes and move them in and
+// out among the taps); the epilogue reads some forty.  The empty asm keeps the compiler from recognising the address and
+// moving these loads up to the others.  The calling kernel's only argument must be its ConvParams (offset 0 of the segment).
+typedef const __attribute__((address_space(4))) ConvParams KernargConvParams;
+__device__ inline KernargConvParams &kernarg_params() {
+  typedef const __attribute__((address_space(4))) char *kernarg_ptr;
+  kernarg_ptr ka = (kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(ka));
+  return *(KernargConvParams *)ka;
+}
+
+// the launch's multiply-shift pairs, read the same way
+__device__ inline ConvRowMath kernarg_row_math() {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return kernarg_params().rm;
+#else
+  return ConvRowMath{};                                // (the host pass only parses device code, and has no copy out of that address space)
+#endif
+}
+
 // Epilogue of every convolution kernel, staged through LDS.
 //
 // The accumulator layout (lane = column, register = row) makes a direct epilogue store 4 bytes per lane, and the
@@ -65,21 +87,19 @@ __device__ inline void mfma_bf16x6(f32x16 &acc, const bf16x8 (&fa)[3], const bf1
 //
 // WK > 1 (strip kernel with the K split across waves): WK waves hold partial sums of the same tile; each writes its own
 // copy of the stage and a unit is the sum of the copies in wave order (deterministic).
-template <int BM, int BN, int WK, int MI, int NI>
-__device__ inline void conv_epilogue(const ConvParams &p, f32x16 (&acc)[MI][NI], float *stage, int m0, int n0, int wm, int wn,
-                                     int half, int l31, int wk = 0) {
+template <int BM, int BN, int WK, bool TIGHT, class Params, int MI, int NI>
+__device__ inline void conv_epilogue_on(const Params &p, f32x16 (&acc)[MI][NI], float *stage, int m0, int n0, int wm, int wn,
+                                        int half, int l31, int wk) {
   constexpr ConvForm F = *find_conv_layout(BM, BN, WK);
   static_assert(MI == F.mi() && NI == F.ni(), "accumulator tiles of the form");
   constexpr int WM = F.wm(), P = F.pitch(), C4 = BN / 4, U = WM * C4 / 8;   // U float4 units per thread and pass
   constexpr int COPY = F.copy_floats();
   const int tid = threadIdx.x;
   const int HW = p.H * p.W;
-  // pictures are powers of two in every benchmark shape: row -> (picture, y, x) by shifts there (an integer division by a run-time
-  // value is ~30 VALU instructions, and the fused pool / image-skip / class-bias paths do several per unit)
-  const bool pow2 = (p.W & (p.W - 1)) == 0 && (HW & (HW - 1)) == 0;
-  const int w_sh = 31 - __builtin_clz(p.W), hw_sh = 31 - __builtin_clz(HW);
-  auto div_hw = [&](int m) { return pow2 ? m >> hw_sh : m / HW; };
-  auto div_w = [&](int r) { return pow2 ? r >> w_sh : r / p.W; };
+  // row -> (time-bias row, picture, y, x, pooled row) by the launch's multiply-shift pairs (dt_conv_rows.h): an integer
+  // division by a run-time value is ~30 VALU instructions, and the time-bias / fused pool / image-skip / class-bias paths do
+  // one or several per unit
+  const ConvRowMath rm = kernarg_row_math();              // (late, wherever `p` itself is read from)
   const bool slab_mode = p.splits > 1;
   const size_t slab_stride = (size_t)p.M * p.cout_p;
   // ---- this thread's units of a pass: row = tid / C4 + k * (256 / C4), four consecutive channels
@@ -127,12 +147,10 @@ __device__ inline void conv_epilogue(const ConvParams &p, f32x16 (&acc)[MI][NI],
   // (n_src > 1: the passes of a dual-output layer, pass i staged at src + i * src_pitch and pooled to pool_out + i * out_pitch)
   auto pool_pass = [&](int mi, float *pool_out, const float *src, int n_src, int src_pitch, size_t out_pitch) __attribute__((always_inline)) {
     __syncthreads();
-    const int Wo = p.W >> 1;
     for (int q0 = tid; q0 < n_src * WM * 8 * C4; q0 += 256) {
       const int pass = q0 / (WM * 8 * C4), q = q0 - pass * (WM * 8 * C4);
       const int pp = q / C4, qc = q % C4, j = pp & 7;
-      const int yy = pow2 ? j >> (w_sh - 1) : j / Wo, xx = j - yy * Wo;
-      const int L0 = 2 * yy * p.W + 2 * xx;
+      const int L0 = pool_window(j, p.W, rm);
       const int m = m0 + (pp >> 3) * (MI * 32) + mi * 32 + L0;
       const int qn = n0 + qc * 4;
       if (m >= p.M || qn >= p.cout_p || (pass && m < p.dup_skip)) continue;
@@ -142,19 +160,28 @@ __device__ inline void conv_epilogue(const ConvParams &p, f32x16 (&acc)[MI][NI],
       f32x4 mx;
 #pragma unroll
       for (int e = 0; e < 4; ++e) mx[e] = fmaxf(fmaxf(a[e], b[e]), fmaxf(c[e], d[e]));
-      const int bimg = div_hw(m), rem = m - bimg * HW;
-      const int y = div_w(rem), x = rem - y * p.W;
-      *reinterpret_cast<f32x4 *>(pool_out + pass * out_pitch + (((size_t)bimg * (p.H >> 1) + (y >> 1)) * Wo + (x >> 1)) * p.cout_p + qn) = mx;
+      *reinterpret_cast<f32x4 *>(pool_out + pass * out_pitch + (size_t)pool_row(row_pixel(m, HW, p.W, rm), p.H, p.W) * p.cout_p + qn) = mx;
     }
   };
   // enc1's 1x1 skip of the <= 3-channel image, recomputed from the NCHW image itself: the value added to unit (m, n..n+3)
-  f32x4 w3r[4];                                        // this thread's four channels: weights of the <= 3 image channels + bias
+  // (this thread's four channels: weights of the <= 3 image channels + bias.  Loaded where a pass uses them, with the pixels,
+  // not once for all passes: sixteen registers that would otherwise stay occupied through every other path of the epilogue)
+  f32x4 w3r[4];
+  // (TIGHT: the fp32 kernels, four waves per SIMD and 128 registers.  They spill through the whole epilogue; the compiler's
+  // allocation is the better one there with these weights loaded once, and with two units per group in the two-pass form)
+  auto load_w3 = [&]() __attribute__((always_inline)) {
+    if (TIGHT) return;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) w3r[e] = p.x3 ? *reinterpret_cast<const f32x4 *>(p.w3 + 4 * (nn + e)) : f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int e = 0; e < 4; ++e) w3r[e] = *reinterpret_cast<const f32x4 *>(p.w3 + 4 * (nn + e));
+  };
+  if (TIGHT) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) w3r[e] = p.x3 ? *reinterpret_cast<const f32x4 *>(p.w3 + 4 * (nn + e)) : f32x4{0.f, 0.f, 0.f, 0.f};
+  }
   auto x3_skip = [&](int m, int) __attribute__((always_inline)) {
     f32x4 r;
-    const int img = div_hw(m), pix = m - img * HW;                 // (x3_hw == H * W)
-    const float *xr = p.x3 + (size_t)(img < p.x3_imgs ? img : img % p.x3_imgs) * p.x3_c * p.x3_hw + pix;
+    const int img = row_div(m, rm.hw), pix = m - img * HW;       // (x3_hw == H * W)
+    const float *xr = p.x3 + (size_t)x3_image(img, p.x3_imgs, rm) * p.x3_c * p.x3_hw + pix;
     const float x0 = xr[0], x1 = p.x3_c > 1 ? xr[p.x3_hw] : 0.f, x2 = p.x3_c > 2 ? xr[2 * p.x3_hw] : 0.f;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -191,44 +218,59 @@ __device__ inline void conv_epilogue(const ConvParams &p, f32x16 (&acc)[MI][NI],
 #pragma unroll
       for (int k = 0; k < U; ++k) {
         mc[k] = ok[k] ? mrow[k] : m0;
-        const int pix = mc[k] - div_hw(mc[k]) * HW, y = div_w(pix), x = pix - y * p.W;
-        cls[k] = 3 * (y == 0 ? 0 : (y == p.H - 1 ? 2 : 1)) + (x == 0 ? 0 : (x == p.W - 1 ? 2 : 1));
+        const RowPixel px = row_pixel(mc[k], HW, p.W, rm);
+        cls[k] = pixel_class(px.y, px.x, p.H, p.W);
       }
 #pragma unroll
-      for (int k = 0; k < U; ++k) rs[k] = p.x3 ? x3_skip(mc[k], nn) : f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int k = 0; k < U; ++k) rs[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (p.x3) load_w3();
+      auto skip_units = [&](int k0, int k1) __attribute__((always_inline)) {
+        if (p.x3) {
+#pragma unroll
+          for (int k = k0; k < k1; ++k) rs[k] = x3_skip(mc[k], nn);
+        }
+      };
+      if (!TIGHT) skip_units(0, U);
       if (p.n_dup == 2 && p.dup_stage2 && p.pool_out) {
         // two passes (the CFG pair), room for a second stage behind the partial-tile copies: both passes' values are formed
         // together (their class-bias loads overlap), staged side by side and pooled in ONE sweep -- two barriers per 32-row
         // pass instead of six (per-workgroup timelines put the pass-after-pass form at 27 us per 256 x 64 tile)
         float *stage2 = stage + WK * COPY;
-        f32x4 b0[U], b1[U];
+        // (four units at a time: both class-bias rows of eight units are 64 registers, next to the eight staged units, their
+        // image skips and the accumulators of the passes to come -- more than the 256-register forms have)
+        constexpr int G = TIGHT ? (U < 2 ? U : 2) : (U < 4 ? U : 4);
 #pragma unroll
-        for (int k = 0; k < U; ++k) {
-          // (32-bit row arithmetic: launch_conv bounds n_dup * M * cout_p by 2^31; a 64-bit division costs ~100 instructions)
-          // (rows below dup_skip have no second pass: their b1 / o1 are formed from a valid row and never stored or pooled)
-          const unsigned r0 = (unsigned)mc[k] / (unsigned)p.m_per_tb;
-          const unsigned r1 = (unsigned)(p.dup_rows + (mc[k] >= p.dup_skip ? mc[k] - p.dup_skip : mc[k])) / (unsigned)p.m_per_tb;
-          b0[k] = *reinterpret_cast<const f32x4 *>(p.tbc + (size_t)r0 * p.tb_stride + cls[k] * p.cout_p + nn);
-          b1[k] = *reinterpret_cast<const f32x4 *>(p.tbc + (size_t)r1 * p.tb_stride + cls[k] * p.cout_p + nn);
-        }
+        for (int k0 = 0; k0 < U; k0 += G) {
+          f32x4 b0[U], b1[U];
+          if (TIGHT) skip_units(k0, k0 + G);
 #pragma unroll
-        for (int k = 0; k < U; ++k) {
-          f32x4 o0 = (v[k] + b0[k]) * sc + sh, o1 = (v[k] + b1[k]) * sc + sh;
-          if (p.relu) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { o0[e] = fmaxf(o0[e], 0.f); o1[e] = fmaxf(o1[e], 0.f); }
+          for (int k = k0; k < k0 + G; ++k) {
+            // (32-bit row arithmetic: launch_conv bounds n_dup * M * cout_p by 2^31)
+            // (rows below dup_skip have no second pass: their b1 / o1 are formed from a valid row and never stored or pooled)
+            const int r0 = row_tb(mc[k], rm), r1 = row_tb(row_dup1(mc[k], p.dup_rows, p.dup_skip), rm);
+            b0[k] = *reinterpret_cast<const f32x4 *>(p.tbc + (size_t)r0 * p.tb_stride + cls[k] * p.cout_p + nn);
+            b1[k] = *reinterpret_cast<const f32x4 *>(p.tbc + (size_t)r1 * p.tb_stride + cls[k] * p.cout_p + nn);
           }
-          o0 += rs[k]; o1 += rs[k];
-          if (ok[k] && !p.skip_out) {
-            *reinterpret_cast<f32x4 *>(p.out + (size_t)mrow[k] * p.cout_p + n) = o0;
-            if (mrow[k] >= p.dup_skip) *reinterpret_cast<f32x4 *>(p.out + ((size_t)p.dup_rows + mrow[k] - p.dup_skip) * p.cout_p + n) = o1;
+#pragma unroll
+          for (int k = k0; k < k0 + G; ++k) {
+            f32x4 o0 = (v[k] + b0[k]) * sc + sh, o1 = (v[k] + b1[k]) * sc + sh;
+            if (p.relu) {
+#pragma unroll
+              for (int e = 0; e < 4; ++e) { o0[e] = fmaxf(o0[e], 0.f); o1[e] = fmaxf(o1[e], 0.f); }
+            }
+            o0 += rs[k]; o1 += rs[k];
+            if (ok[k] && !p.skip_out) {
+              *reinterpret_cast<f32x4 *>(p.out + (size_t)mrow[k] * p.cout_p + n) = o0;
+              if (mrow[k] >= p.dup_skip) *reinterpret_cast<f32x4 *>(p.out + ((size_t)p.dup_rows + mrow[k] - p.dup_skip) * p.cout_p + n) = o1;
+            }
+            *reinterpret_cast<f32x4 *>(stage + (row0 + k * (256 / C4)) * P + c4 * 4) = o0;
+            *reinterpret_cast<f32x4 *>(stage2 + (row0 + k * (256 / C4)) * P + c4 * 4) = o1;
           }
-          *reinterpret_cast<f32x4 *>(stage + (row0 + k * (256 / C4)) * P + c4 * 4) = o0;
-          *reinterpret_cast<f32x4 *>(stage2 + (row0 + k * (256 / C4)) * P + c4 * 4) = o1;
         }
         pool_pass(mi, p.pool_out, stage, 2, WK * COPY, (size_t)((p.dup_rows - p.dup_skip) >> 2) * p.cout_p);
         continue;
       }
+      if (TIGHT) skip_units(0, U);
       for (int pass = 0; pass < p.n_dup; ++pass) {
         // dup_skip is a multiple of 256 rows and m0 of the tile height (64 / 128 / 256): a workgroup's rows all lie on one side
         if (pass && m0 < p.dup_skip) break;                              // (block-uniform) single-pass images: no second pass
@@ -239,7 +281,7 @@ __device__ inline void conv_epilogue(const ConvParams &p, f32x16 (&acc)[MI][NI],
           o[k] = f32x4{0.f, 0.f, 0.f, 0.f};
           if (ok[k]) {
             const size_t mg = (size_t)shift + mrow[k];
-            const unsigned tr = (unsigned)(shift + mrow[k]) / (unsigned)p.m_per_tb;
+            const int tr = row_tb(shift + mrow[k], rm);
             const f32x4 b = *reinterpret_cast<const f32x4 *>(p.tbc + (size_t)tr * p.tb_stride + cls[k] * p.cout_p + n);
             o[k] = (v[k] + b) * sc + sh;
             if (p.relu) {
@@ -279,7 +321,7 @@ __device__ inline void conv_epilogue(const ConvParams &p, f32x16 (&acc)[MI][NI],
 #pragma unroll
       for (int k = 0; k < U; ++k) {
         t[k] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (ok[k]) t[k] = *reinterpret_cast<const f32x4 *>(p.tb + (size_t)(mrow[k] / p.m_per_tb) * p.tb_stride + n);
+        if (ok[k]) t[k] = *reinterpret_cast<const f32x4 *>(p.tb + (size_t)row_tb(mrow[k], rm) * p.tb_stride + n);
       }
 #pragma unroll
       for (int k = 0; k < U; ++k) v[k] += t[k];
@@ -295,6 +337,7 @@ __device__ inline void conv_epilogue(const ConvParams &p, f32x16 (&acc)[MI][NI],
       for (int k = 0; k < U; ++k) v[k] += a[k];
     }
     if (p.x3) {
+      load_w3();
 #pragma unroll
       for (int k = 0; k < U; ++k)
         if (ok[k]) v[k] += x3_skip(mrow[k], nn);
@@ -340,6 +383,14 @@ __device__ inline void conv_epilogue(const ConvParams &p, f32x16 (&acc)[MI][NI],
       pool_pass(mi, p.pool_out, stage, 1, 0, 0);
     }
   }
+}
+
+// LATE: read the arguments from the kernel-argument segment (kernarg_params), otherwise from the kernel's own copy `p`
+template <int BM, int BN, int WK, bool LATE, bool TIGHT = false, int MI, int NI>
+__device__ inline void conv_epilogue(const ConvParams &p, f32x16 (&acc)[MI][NI], float *stage, int m0, int n0, int wm, int wn,
+                                     int half, int l31, int wk = 0) {
+  if constexpr (LATE) conv_epilogue_on<BM, BN, WK, TIGHT>(kernarg_params(), acc, stage, m0, n0, wm, wn, half, l31, wk);
+  else conv_epilogue_on<BM, BN, WK, TIGHT>(p, acc, stage, m0, n0, wm, wn, half, l31, wk);
 }
 
 // relu(acc*scale+shift) in registers, between the main K walk and the fused skip walk

@@ -100,15 +100,11 @@ __global__ __launch_bounds__(256, find_strip_form(BM, BN, KC, WK)->waves_per_sim
     const int row_i = wm * (MI * 32) + mi * 32 + l31;
     const int m = m0 + row_i;
     a_row[mi] = row_i + halo;
+    const ConvRowMath rm = kernarg_row_math();                    // (not p.rm: these pairs would then hold scalar registers through the walk)
     unsigned mask = 0;
     if (m < p.M) {
-      const int rem = m % HW;
-      const int y = rem / p.W, x = rem - y * p.W;
-#pragma unroll
-      for (int t = 0; t < 9; ++t) {
-        const int yy = y + t / 3 - 1, xx = x + t % 3 - 1;
-        if (yy >= 0 && yy < p.H && xx >= 0 && xx < p.W) mask |= 1u << t;
-      }
+      const RowPixel px = row_pixel(m, HW, p.W, rm);
+      mask = pixel_tap_mask(px.y, px.x, p.H, p.W);
     }
     a_mask[mi] = mask;
   }
@@ -441,7 +437,7 @@ __global__ __launch_bounds__(256, find_strip_form(BM, BN, KC, WK)->waves_per_sim
     for (int ch = n_main; ch < n_chunks; ++ch)                     // fused 1x1 skip walk through the strip: centre tap only
       do_step(std::integral_constant<int, 4>{}, ch, true, true, ch + 1 < n_chunks, ADV_SKIP);
   }
-  conv_epilogue<BM, BN, WK>(p, acc, reinterpret_cast<float *>(strip_lds), m0, n0, wm, wn, half, l31, wk);
+  conv_epilogue<BM, BN, WK, WK == 1>(p, acc, reinterpret_cast<float *>(strip_lds), m0, n0, wm, wn, half, l31, wk);
 }
 
 #define DT_STRIP_ROW(cls, kind, bm, bn, kc, wk) {{kind, bm, bn, kc, wk, cls}, conv_strip_bf16x6_kernel<bm, bn, kc, wk>},

@@ -6,6 +6,7 @@
 
 #include "../../include/dt_hip.h"
 #include "dt_conv_forms.h"
+#include "dt_conv_rows.h"
 
 #define DT_HIP_TRY(expr)                         \
   do {                                           \
@@ -83,7 +84,8 @@ struct ConvParams {
   int tap_lo, tap_hi;  // taps visited (a 1x1 image only sees the centre tap)
   int relu;
   int tb_stride;       // floats between time-bias rows
-  int m_per_tb;        // GEMM rows sharing one time-bias row
+  int m_per_tb;        // GEMM rows sharing one time-bias row: any value >= 1, down to H * W (a row per sample); the kernels get
+                       // m / m_per_tb from row_tb(m, rm) (dt_conv_rows.h), never from a division
   // split-K over taps: grid.z = splits, each z walks (tap_hi-tap_lo)/splits taps and stores its raw
   // accumulators to slab[z][M][cout_p]; splitk_epilogue then sums the slabs in z order (deterministic)
   int splits;
@@ -133,6 +135,9 @@ struct ConvParams {
   // layers with an odd chunk count (cin_p = 48, 80, 112, 208, 240: size factors 0.3, 0.4, 0.6, 0.8, 0.9): the walk is
   // ceil(chunks / step) steps, the activation loads of a chunk >= cin_p / 16 are replaced by zeros
   int ccw, ccw2;
+  // multiply-shift pairs of the launch's run-time divisors (dt_conv_rows.h): filled by launch_conv from H, W, m_per_tb and
+  // x3_imgs, whatever the caller left here
+  ConvRowMath rm;
 };
 
 int launch_conv(const ConvParams &p, hipStream_t s);
