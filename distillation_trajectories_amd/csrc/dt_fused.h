@@ -1,4 +1,5 @@
-// Declarations of the whole-forward kernel for small U-Nets (dt_fused.hip), shared with the host side in dt_unet.hip.
+// Declarations of the whole-forward kernel for small U-Nets (dt_fused.hip), shared with its host side: the pack at create time
+// (build_fused, dt_unet.hip), the forward (dt_unet_forward.hip) and the sampler loop (dt_sample.hip).
 #pragma once
 #include "dt_internal.h"
 
@@ -6,6 +7,11 @@ namespace dt {
 
 constexpr int kFusedMaxSteps = 64;     // timesteps per launch (their coefficients travel in the kernel arguments)
 constexpr int kFusedMaxOps = 24;
+constexpr size_t kFusedLdsLimit = 160 * 1024;   // dynamic LDS bytes a workgroup of the kernel may ask for
+// The parameter block (kept in LDS): per block the folded BN vectors of conv1 / conv2 and the skip conv's bias, cout_p floats
+// each (5 * tb_cols in all), then enc1's image-skip rows [c0p][4].  tb_cols: FusedLds::tb_cols.
+constexpr int fused_par_w3(int tb_cols) { return 5 * tb_cols; }
+constexpr int fused_par_floats(int tb_cols, int c0p) { return fused_par_w3(tb_cols) + 4 * c0p; }
 
 enum { FUSED_OP_FIRST = 0, FUSED_OP_CONV, FUSED_OP_UP, FUSED_OP_HEAD };
 // what follows relu(bn(conv)) in a convolution's epilogue
@@ -69,7 +75,6 @@ struct FusedArgs {
 
 bool fused_eligible(int C, int c0p, int c1p);
 FusedLds fused_lds(int G, int c0p, int c1p);
-size_t fused_lds_bytes(int G, int c0p, int c1p);
 int fused_ops(const FusedModel &m, int G, FusedOp *ops);      // fills at most kFusedMaxOps entries, returns the count
 double fused_flops_per_row(int C, int c0, int c1);
 int launch_pack_fused_first(const float *w_oihw, float *dst, int cout, int C, int ot, hipStream_t s);

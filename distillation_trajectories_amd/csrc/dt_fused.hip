@@ -604,7 +604,7 @@ FusedLds fused_lds(int G, int c0p, int c1p) {
   L.scr = L.head + 4 * c0p + 4;                    // partial tiles of K-split units: kWaves x 64 lanes x 4
   L.par = L.scr + kWaves * 256;                    // the model's small vectors: 5 x cout_p per block + the image-skip rows
   L.tb_cols = 2 * c0p + 6 * c1p;                   // padded out-channels of the eight blocks = columns of a time-bias row in use
-  L.tb = L.par + 5 * L.tb_cols + 4 * c0p;          // [G][tb_cols] rows of the current step
+  L.tb = L.par + fused_par_floats(L.tb_cols, c0p); // [G][tb_cols] rows of the current step
   L.b = L.tb + G * L.tb_cols;
   L.c = L.b + a_sz;
   L.e = L.c + 4 * u;
@@ -613,8 +613,6 @@ FusedLds fused_lds(int G, int c0p, int c1p) {
   if (L.c + 256 * G * s0 > L.total) L.total = L.c + 256 * G * s0;      // H0 [256 G][s0]
   return L;
 }
-
-size_t fused_lds_bytes(int G, int c0p, int c1p) { return (size_t)fused_lds(G, c0p, c1p).total * sizeof(float); }
 
 // The layer table of one forward for G rows per workgroup (host memory; the caller uploads it).  Buffers:
 //   H0 enc1.conv1 out -> C (overlay) | P1 pooled enc1 -> B | H2 -> C | O2 -> D (skip of dec1, lives to the end) | P2 -> E'
@@ -716,9 +714,9 @@ int launch_unet_fused(const FusedArgs &a, hipStream_t s) {
   {
     std::lock_guard<std::mutex> lock(attr_mu);
     if (attr_status[dev] == 0) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&unet_fused_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&unet_fused_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFusedLdsLimit);
       if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&unet_fused_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&unet_fused_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFusedLdsLimit);
       attr_status[dev] = e == hipSuccess ? 1 : -(int)e;
     }
     if (attr_status[dev] != 1) return -attr_status[dev];
@@ -727,7 +725,7 @@ int launch_unet_fused(const FusedArgs &a, hipStream_t s) {
   if (a.mk.mask && (!a.mk.known || a.mode != FUSED_LOOP)) return a.mk.known ? DT_E_ARG : DT_E_NULL;
   if (a.mode == FUSED_LOOP && (a.n_steps < 1 || a.n_steps > kFusedMaxSteps)) return DT_E_ARG;
   const size_t lds = (size_t)a.lds.total * sizeof(float);
-  if (lds > 160 * 1024) return DT_E_SHAPE;
+  if (lds > kFusedLdsLimit) return DT_E_SHAPE;
   const int Bt = a.B * a.n_pass - a.B_single * (a.n_pass - 1);
   int grid;
   if (a.mode == FUSED_FORWARD) {

@@ -7,6 +7,7 @@
 #include "../../include/dt_hip.h"
 #include "dt_conv_forms.h"
 #include "dt_conv_rows.h"
+#include "dt_unet_layout.h"
 
 #define DT_HIP_TRY(expr)                         \
   do {                                           \
@@ -35,6 +36,7 @@ struct ProfileScope {
   hipStream_t stream;
   void *end_event;
 };
+bool profiling_on();   // between dt_profile_begin and dt_profile_end (dt_profile.hip)
 
 // bilinear source coordinates for scale factor 2 with align_corners=True (ATen area_pixel_compute_scale:
 // scale = (in-1)/(out-1), 0 when out == 1; src = scale*dst), and the four-tap blend with its operation order fixed by
@@ -53,18 +55,11 @@ __device__ inline float bilinear_blend(float v00, float v01, float v10, float v1
   return fmaf(wy1, bot, wy0 * top);
 }
 
-constexpr int kChanPad = 16;   // activation channel granularity (= BK of the conv GEMM)
-constexpr int kNPad = 64;      // packed-weight N granularity (smallest BN tile)
-constexpr int kBlocks = 8;
-constexpr int kChunkPad = 4;   // chunk granularity of the split-bf16 weight packs (see ConvParams::ccw)
-
-inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+// (kChanPad, kNPad, kBlocks, kChunkPad, kSplitMaxRows, round_up and pack_chunks: dt_unet_layout.h)
 // 256-thread blocks of a grid-stride launch over `total` items, at most `cap` (each launcher's own)
 inline int grid_blocks(size_t total, int cap) { return (int)((total + 255) / 256 < (size_t)cap ? (total + 255) / 256 : (size_t)cap); }
 // whether a walk of `cc` chunks in groups of `div` (K chunks per step x split-K slices) stays inside a pack of `ccw` chunks
 inline bool chunks_fit(int cc, int ccw, int div) { return div >= 1 && round_up(cc, div) <= ccw; }
-// 16-channel weight chunks per tap of a split-bf16 pack of cin_p input channels (zero chunks up to a multiple of kChunkPad)
-inline int pack_chunks(int cin_p) { return round_up(cin_p, 16 * kChunkPad) >> 4; }
 
 // One convolution expressed as an implicit GEMM over NHWC activations:
 //   out[m][n] = epilogue( sum_{tap,c} in[pixel(m)+tap][c] * w[tap][c][n] )
@@ -154,7 +149,6 @@ inline const ConvKernel &conv_kernel_of(const ConvKernel (&table)[N], const Conv
 // cin_w: padded input channels per tap of the pack (>= cin_p, multiple of 16 * kChunkPad; zeros beyond cin_p)
 int launch_pack_conv_bf16x3(const float *w_oihw, void *wp, int cout, int cin, int ksize, int cin_p, int cin_w, int n_p,
                             int split_c, int split_cp, hipStream_t s);
-constexpr int kSplitMaxRows = 32768;   // split-K candidates only below this many GEMM rows (bounds the slab)
 
 // ---- launch rules of a convolution (dt_conv.hip): which choices exist, how a requested one resolves for a layer, and
 // whether a bound launch can run.  Every caller (the forward, the choice hooks, the autotuner, the launchers) goes through them.

@@ -1,6 +1,6 @@
 // Host-side sanitizer driver ("ASan host build"): links the library's own translation units compiled with
 // -Xarch_host -fsanitize=address,undefined (device code is NOT instrumented: GPU ASan is unavailable on this pool) and walks the
-// host code of dt_unet.hip through the C ABI -- weight packing, launch plans (heuristic, pinned, autotuned, keyed by the full forward
+// host code of the U-Net handle (dt_unet.hip, dt_unet_forward.hip, dt_unet_tune.hip, dt_sample.hip, dt_profile.hip) through the C ABI -- weight packing, launch plans (heuristic, pinned, autotuned, keyed by the full forward
 // shape), forward / mixed forward, the sampler loops (plain and hipGraph replay), the in-library profiler, the metric launchers and the
 // argument-error paths.  Exit status 0 and "driver ok" on stdout mean no sanitizer report and no unexpected status.
 // Built by distillation_trajectories_amd/csrc/build.py (build_sanitizer_driver); run by tests/test_host_sanitize.py on the GPU box.
