@@ -17,6 +17,7 @@
 // of consecutive channels for two pixel rows -> coalesced NHWC stores.
 // The split-K slice arithmetic of the K walk, its chunk carry and the hand-over to the fused skip walk are KWalk of
 // dt_conv_walk.h, shared with dt_conv_bf16.hip; that header also says what of the walk stays spelled out here, and why.
+#include "dt_conv_strip_pair.h"
 #include "dt_conv_walk.h"
 
 namespace dt {
@@ -141,7 +142,9 @@ int launch_splitk_epilogue(const ConvParams &p, hipStream_t s);
 #define DT_GEMM_ROW(cls, kind, bm, bn, kc, wk) {{kind, bm, bn, kc, wk, cls}, conv_gemm_kernel<bm, bn>},
 static const ConvKernel kGemmKernels[] = {DT_CONV_FORMS_FP32(DT_GEMM_ROW)};
 
-int launch_conv(const ConvParams &p_in, hipStream_t s) {
+int launch_conv(const ConvParams &p_in, hipStream_t s) { return launch_conv(p_in, s, false); }
+
+int launch_conv(const ConvParams &p_in, hipStream_t s, bool strip_pair) {
   ConvParams p = p_in;
   if (!p.in || !p.w || !p.scale || !p.shift || !p.out) return DT_E_NULL;
   if (p.H < 1 || p.W < 1) return DT_E_SHAPE;
@@ -152,11 +155,13 @@ int launch_conv(const ConvParams &p_in, hipStream_t s) {
   {
     // algorithmic flops: what the reference's conv2d does on the unpadded shape (all ksize^2 taps)
     const double flops = 2.0 * p.M * (double)p.cout_real * ((double)p.cin_real * p.ksize * p.ksize + (p.in2 ? p.cin2_real : 0));
-    ProfileScope prof(find_conv_form(p.kind, p.bm, p.bn)->cls, flops, 4.0 * p.M * ((double)p.cin_real + p.cout_real), s);
+    // (a launch the pair kernel serves keeps its form, and is profiled under the pair kernel's own class)
+    const bool pair = strip_pair && strip_pair_serves(p);
+    ProfileScope prof(pair ? KC_CONVS_PAIR : find_conv_form(p.kind, p.bm, p.bn)->cls, flops, 4.0 * p.M * ((double)p.cin_real + p.cout_real), s);
     if (p.kind == KIND_FP32) {
       conv_kernel_of(kGemmKernels, p).fn<<<dim3((p.M + p.bm - 1) / p.bm, p.n_p / p.bn, p.splits), 256, 0, s>>>(p);
       DT_LAUNCH_CHECK();
-    } else if (const int st = is_strip(p.kind) ? launch_conv_strip(p, s) : launch_conv_bf16x6(p, s)) return st;
+    } else if (const int st = pair ? launch_conv_strip_pair(p, s) : (is_strip(p.kind) ? launch_conv_strip(p, s) : launch_conv_bf16x6(p, s))) return st;
   }
   return p.splits > 1 ? launch_splitk_epilogue(p, s) : DT_OK;
 }

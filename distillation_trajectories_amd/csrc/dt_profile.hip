@@ -5,7 +5,7 @@
 #include <mutex>
 #include <vector>
 
-#include "dt_internal.h"
+#include "dt_conv_strip_pair.h"
 
 using namespace dt;
 
@@ -38,6 +38,7 @@ const char *class_name(int cls) {
 #define DT_STRIP(c, kind, bm, bn, kc, wk) case c: return "conv_strip_bf16x6_kernel<" #bm "," #bn ">";
 #define DT_STRIPK(c, kind, bm, bn, kc, wk) case c: return "conv_strip_bf16x6_kernel<" #bm "," #bn ",K" #kc ">";
     DT_CONV_FORMS_FP32(DT_GEMM) DT_CONV_FORMS_BF16(DT_BF16) DT_CONV_FORMS_STRIP(DT_STRIP) DT_CONV_FORMS_STRIPK(DT_STRIPK)
+    case KC_CONVS_PAIR: return "conv_strip_pair_bf16x6_kernel<256,128>";   // (dt_conv_strip_pair.h)
     default: return kClassName[cls - KC_CONV_COUNT];
   }
 }
@@ -91,10 +92,10 @@ int dt_profile_end(void) {
   return DT_OK;
 }
 
-int dt_profile_class_count(void) { return KC_COUNT; }
+int dt_profile_class_count(void) { return KC_COUNT_ALL; }
 
 int dt_profile_read(int cls, const char **name, long long *launches, double *ms, double *flops, double *bytes) {
-  if (cls < 0 || cls >= KC_COUNT || !launches || !ms || !flops || !bytes) return DT_E_ARG;
+  if (cls < 0 || cls >= KC_COUNT_ALL || !launches || !ms || !flops || !bytes) return DT_E_ARG;
   if (name) *name = class_name(cls);
   *launches = 0; *ms = 0; *flops = 0; *bytes = 0;
   std::lock_guard<std::mutex> lock(g_prof.mu);

@@ -176,6 +176,7 @@ int dt_unet_create(const dt_unet_desc *desc, const float *const *bt, const float
   std::unique_ptr<dt_unet> u(new (std::nothrow) dt_unet());
   if (!u) return (int)hipErrorOutOfMemory;
   u->geo = geo;
+  u->strip_pair = getenv("DT_NO_STRIP_PAIR") == nullptr;
   const SlabLayout L = slab_layout(geo);
   DT_HIP_TRY(hipMalloc((void **)&u->slab, L.total * sizeof(float)));
   if (const int st = pack_slab(u.get(), L, bt, gt, s)) return st;

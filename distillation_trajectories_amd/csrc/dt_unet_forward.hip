@@ -136,7 +136,7 @@ int run_block(const dt_unet *u, const ResolvedForward &f, int j, const float *in
       if (slot == 1) p.in_b = ws + pl.o[skip];
       if (slot == 2) p.in2_b = ws + pl.o[skip];
     }
-    const int st = launch_conv(p, s);
+    const int st = launch_conv(p, s, u->strip_pair);
     if (st) return st;
   }
   return DT_OK;

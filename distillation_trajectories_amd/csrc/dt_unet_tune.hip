@@ -24,12 +24,12 @@ struct ConvTimer {
   // *ms: average milliseconds of `reps` back-to-back launches of q after one warm launch: in the sampler launches queue
   // behind each other, so a launch is not charged the idle-queue launch latency per kernel (which would bias against
   // split launches = two kernels).  Returns the status of the launches.
-  int time(const ConvParams &q, int reps, hipStream_t s, float *ms) {
+  int time(const ConvParams &q, bool strip_pair, int reps, hipStream_t s, float *ms) {
     *ms = 0.f;
-    int st = launch_conv(q, s);
+    int st = launch_conv(q, s, strip_pair);
     if (st != DT_OK) return st;
     (void)hipEventRecord(e0, s);
-    for (int rep = 0; rep < reps && st == DT_OK; ++rep) st = launch_conv(q, s);
+    for (int rep = 0; rep < reps && st == DT_OK; ++rep) st = launch_conv(q, s, strip_pair);
     (void)hipEventRecord(e1, s);
     if (hipEventSynchronize(e1) != hipSuccess) st = (int)hipGetLastError();
     if (st != DT_OK) return st;
@@ -98,13 +98,13 @@ int dt_unet_autotune(dt_unet *h, int batch_total, int H, int W, int images, int 
   {   // The clocks of an idle GPU take tens of milliseconds of load to settle (the same launch measures 15 % slower
       // cold): run one mid-sized layer for a while first so that the first candidates are not timed against a ramp.
     const ConvParams wp = bind_conv(h, f, 1, 1, f.c[1][1], ws + pl.input(1), ws, pl, tb, batch_total);
-    for (int rep = 0; rep < 200 && st == DT_OK; ++rep) st = launch_conv(wp, s);
+    for (int rep = 0; rep < 200 && st == DT_OK; ++rep) st = launch_conv(wp, s, h->strip_pair);
     if (hipStreamSynchronize(s) != hipSuccess) st = (int)hipGetLastError();
   }
   // the timed average of one candidate; < 0: the launch cannot run here
   auto measure = [&](const ConvParams &q, int reps) -> float {
     float ms;
-    const int lst = timer.time(q, reps, s, &ms);
+    const int lst = timer.time(q, h->strip_pair, reps, s, &ms);
     if (lst != DT_OK && lst != DT_E_SHAPE && lst != DT_E_ARG) st = lst;
     return lst == DT_OK ? ms : -1.f;
   };
@@ -181,7 +181,7 @@ int dt_unet_time_conv(const dt_unet *h, int batch_total, int H, int W, int image
   *flops = 2.0 * p.M * (double)p.cout_real * ((double)p.cin_real * p.ksize * p.ksize + (p.in2 ? p.cin2_real : 0));
   ConvTimer timer;
   if (const int bad = timer.create()) return bad;
-  return timer.time(p, reps, (hipStream_t)stream, ms);
+  return timer.time(p, h->strip_pair, reps, (hipStream_t)stream, ms);
 }
 
 /* test / report hook: the (bm, bn, splits) in use for block j, slot (0 skip, 1 conv1, 2 conv2) at a shape */
