@@ -13,7 +13,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["dt_conv.hip", "dt_conv_bf16.hip", "dt_conv_strip.hip", "dt_conv_strip_pair.hip", "dt_layers.hip", "dt_update.hip", "dt_metrics.hip", "dt_fused.hip", "dt_profile.hip", "dt_unet.hip",
            "dt_unet_forward.hip", "dt_unet_tune.hip", "dt_sample.hip", "dt_featnet.hip", "dt_inception.hip", "dt_pca.hip", "dt_fid.hip", "dt_lpips.hip", "dt_tsne.hip", "dt_quality.hip", "dt_quality_stream.hip", "dt_edit.hip", "dt_rng.hip"]
-HEADERS = ["dt_internal.h", "dt_conv_forms.h", "dt_conv_rows.h", "dt_batch.h", "dt_dense64.h", "dt_quality_math.h", "dt_featnet.h", "dt_conv_epilogue.h", "dt_conv_walk.h", "dt_conv_strip_pair.h", "dt_update_math.h", "dt_fused.h", "dt_unet.h", "dt_unet_layout.h", os.path.join("..", "..", "include", "dt_hip.h"),
+HEADERS = ["dt_internal.h", "dt_conv_forms.h", "dt_conv_rows.h", "dt_batch.h", "dt_dense64.h", "dt_quality_math.h", "dt_featnet.h", "dt_conv_epilogue.h", "dt_conv_walk.h", "dt_conv_strip_kernel.h", "dt_conv_strip_pair.h", "dt_update_math.h", "dt_fused.h", "dt_unet.h", "dt_unet_layout.h", os.path.join("..", "..", "include", "dt_hip.h"),
            os.path.join("..", "..", "include", "dt_hip_noise.h"),
            os.path.join("..", "..", "include", "dt_hip_inception.h"),
            os.path.join("..", "..", "include", "dt_hip_pca.h"),

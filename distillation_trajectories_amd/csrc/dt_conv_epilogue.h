@@ -87,14 +87,19 @@ __device__ inline ConvRowMath kernarg_row_math() {
 //
 // WK > 1 (strip kernel with the K split across waves): WK waves hold partial sums of the same tile; each writes its own
 // copy of the stage and a unit is the sum of the copies in wave order (deterministic).
-template <int BM, int BN, int WK, bool TIGHT, class Params, int MI, int NI>
+//
+// The passes below are laid out for 256 threads.  TID_MASK = 0: the workgroup has 256 threads and a thread's index is
+// threadIdx.x.  TID_MASK = 255: a larger workgroup whose every 256 consecutive threads form one such group with its own
+// tile (m0, n0) and its own `stage` (the N halves of the strip kernel); the index is that within the group.  Nothing else
+// of the workgroup's shape is read here, and every barrier is uniform over the whole workgroup.
+template <int BM, int BN, int WK, bool TIGHT, int TID_MASK, class Params, int MI, int NI>
 __device__ inline void conv_epilogue_on(const Params &p, f32x16 (&acc)[MI][NI], float *stage, int m0, int n0, int wm, int wn,
                                         int half, int l31, int wk) {
   constexpr ConvForm F = *find_conv_layout(BM, BN, WK);
   static_assert(MI == F.mi() && NI == F.ni(), "accumulator tiles of the form");
   constexpr int WM = F.wm(), P = F.pitch(), C4 = BN / 4, U = WM * C4 / 8;   // U float4 units per thread and pass
   constexpr int COPY = F.copy_floats();
-  const int tid = threadIdx.x;
+  const int tid = TID_MASK ? (int)(threadIdx.x & (unsigned)TID_MASK) : (int)threadIdx.x;
   const int HW = p.H * p.W;
   // row -> (time-bias row, picture, y, x, pooled row) by the launch's multiply-shift pairs (dt_conv_rows.h): an integer
   // division by a run-time value is ~30 VALU instructions, and the time-bias / fused pool / image-skip / class-bias paths do
@@ -386,11 +391,11 @@ __device__ inline void conv_epilogue_on(const Params &p, f32x16 (&acc)[MI][NI], 
 }
 
 // LATE: read the arguments from the kernel-argument segment (kernarg_params), otherwise from the kernel's own copy `p`
-template <int BM, int BN, int WK, bool LATE, bool TIGHT = false, int MI, int NI>
+template <int BM, int BN, int WK, bool LATE, bool TIGHT = false, int TID_MASK = 0, int MI, int NI>
 __device__ inline void conv_epilogue(const ConvParams &p, f32x16 (&acc)[MI][NI], float *stage, int m0, int n0, int wm, int wn,
                                      int half, int l31, int wk = 0) {
-  if constexpr (LATE) conv_epilogue_on<BM, BN, WK, TIGHT>(kernarg_params(), acc, stage, m0, n0, wm, wn, half, l31, wk);
-  else conv_epilogue_on<BM, BN, WK, TIGHT>(p, acc, stage, m0, n0, wm, wn, half, l31, wk);
+  if constexpr (LATE) conv_epilogue_on<BM, BN, WK, TIGHT, TID_MASK>(kernarg_params(), acc, stage, m0, n0, wm, wn, half, l31, wk);
+  else conv_epilogue_on<BM, BN, WK, TIGHT, TID_MASK>(p, acc, stage, m0, n0, wm, wn, half, l31, wk);
 }
 
 // relu(acc*scale+shift) in registers, between the main K walk and the fused skip walk

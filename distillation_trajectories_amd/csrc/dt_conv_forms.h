@@ -119,6 +119,16 @@ struct ConvForm {
   constexpr bool needs_lds_attribute() const { return lds_limit() > 65536; }   // above what a kernel may take by default
   // whether a strip form runs on picture rows of W pixels (staging reach, LDS)
   constexpr bool reaches(int W) const { return W <= max_w() && lds_bytes(W) <= lds_limit(); }
+
+  // ---- a strip workgroup that walks NH adjacent N tiles of the form over ONE staged strip (conv_strip_bf16x6_kernel's NH,
+  // dt_conv_strip_kernel.h; NH = 2 is the pair kernel, dt_conv_strip_pair.h): 256 threads per half, all of them stage the
+  // strip, the halves' weight tiles lie side by side, and each half has an epilogue stage of its own, far enough from
+  // the next for the second stage of a two-pass epilogue whether the launch has one or not.  Kernel and launcher both
+  // read these.
+  constexpr int threads(int nh) const { return 256 * nh; }
+  constexpr int ap(int nh) const { return nh == 1 ? ap() : (2 * (bm + 2 * (max_w() + 1)) + threads(nh) - 1) / threads(nh); }
+  constexpr int plane_b(int nh) const { return plane_b() * nh; }
+  constexpr int half_stage_floats() const { return stage_floats() + copy_floats(); }
 };
 
 #define DT_X(cls, kind, bm, bn, kc, wk) {kind, bm, bn, kc, wk, cls},

@@ -28,8 +28,6 @@
 // waves: there the taps of a pair are split across waves (FusedOp::ks) and the partial tiles meet in LDS.
 //
 // The layer sequence is a small table (FusedOp) built on the host; LDS buffer placement is in fused_lds() below.
-#include <mutex>
-
 #include "dt_conv_epilogue.h"
 #include "dt_update_math.h"
 #include "dt_fused.h"
@@ -704,23 +702,10 @@ double fused_flops_per_row(int C, int c0, int c1) {
 }
 
 int launch_unet_fused(const FusedArgs &a, hipStream_t s) {
-  // the runtime keeps the dynamic-LDS attribute per device: set on the first launch on each device (launches come from several host threads)
-  constexpr int kMaxDevices = 64;
-  static std::mutex attr_mu;
-  static int attr_status[kMaxDevices];   // 0 not set yet, 1 set, otherwise -(hip error)
-  int dev = 0;
-  DT_HIP_TRY(hipGetDevice(&dev));
-  if (dev < 0 || dev >= kMaxDevices) return DT_E_ARG;
-  {
-    std::lock_guard<std::mutex> lock(attr_mu);
-    if (attr_status[dev] == 0) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&unet_fused_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFusedLdsLimit);
-      if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&unet_fused_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFusedLdsLimit);
-      attr_status[dev] = e == hipSuccess ? 1 : -(int)e;
-    }
-    if (attr_status[dev] != 1) return -attr_status[dev];
-  }
+  static const LdsLimit limits[] = {{reinterpret_cast<const void *>(&unet_fused_kernel<false>), kFusedLdsLimit},
+                                    {reinterpret_cast<const void *>(&unet_fused_kernel<true>), kFusedLdsLimit}};
+  static LdsLimitOnce lds_limit;
+  if (const int st = lds_limit.raise(limits, 2)) return st;
   if (a.G != 2 || a.n_ops < 1 || !a.ops) return DT_E_ARG;      // (the kernel's update slots per thread are sized for G = 2)
   if (a.mk.mask && (!a.mk.known || a.mode != FUSED_LOOP)) return a.mk.known ? DT_E_ARG : DT_E_NULL;
   if (a.mode == FUSED_LOOP && (a.n_steps < 1 || a.n_steps > kFusedMaxSteps)) return DT_E_ARG;

@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <mutex>
+
 #include "../../include/dt_hip.h"
 #include "dt_conv_forms.h"
 #include "dt_conv_rows.h"
@@ -22,11 +24,41 @@
 
 namespace dt {
 
+// ---- a kernel family's dynamic-LDS limit above the 64 KB a kernel may take by default.  The runtime keeps that attribute
+// per device, so it is raised on the family's first launch on each device, not once per process.  One object per family
+// (a function-local static of its launcher): a failure is remembered per device, returned by every later launch there,
+// and marks no other family.
+struct LdsLimit { const void *fn; size_t bytes; };
+class LdsLimitOnce {
+ public:
+  // DT_OK once every kernel of `list` has its limit on the current device; otherwise the first error (remembered)
+  int raise(const LdsLimit *list, size_t n) {
+    int dev = 0;
+    DT_HIP_TRY(hipGetDevice(&dev));
+    if (dev < 0 || dev >= kMaxDevices) return DT_E_ARG;
+    std::lock_guard<std::mutex> lock(mu_);   // launches come from several host threads
+    if (status_[dev] == 0) {
+      status_[dev] = 1;
+      for (size_t i = 0; i < n && status_[dev] == 1; ++i) {
+        const hipError_t e = hipFuncSetAttribute(list[i].fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)list[i].bytes);
+        if (e != hipSuccess) status_[dev] = -(int)e;
+      }
+    }
+    return status_[dev] == 1 ? DT_OK : -status_[dev];
+  }
+
+ private:
+  static constexpr int kMaxDevices = 64;
+  std::mutex mu_;
+  int status_[kMaxDevices] = {};             // 0 not set yet, 1 set, otherwise -(hip error)
+};
+
 // ---- optional per-launch timing with HIP events on the launch stream (bench.py roofline numbers).
 // Off by default; when on, every instrumented launch is bracketed by two event records.
 enum KernelClass {   // the convolution classes come first: ConvClass (dt_conv_forms.h)
   KC_SPLITK_EPILOGUE = KC_CONV_COUNT, KC_FIRST_CONV, KC_POOL, KC_UPCAT, KC_HEAD, KC_HEAD_UP, KC_TIME_BIAS, KC_UPDATE, KC_METRICS,
   KC_WASSERSTEIN, KC_RESAMPLE, KC_FUSED, KC_PAIR_METRICS,
+  KC_CONVS_PAIR,     // launches that the strip kernel's NH = 2 form serves (dt_conv_strip_pair.h): not a ConvClass, it has no form row
   KC_COUNT
 };
 struct ProfileScope {

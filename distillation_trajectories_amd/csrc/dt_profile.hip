@@ -5,7 +5,7 @@
 #include <mutex>
 #include <vector>
 
-#include "dt_conv_strip_pair.h"
+#include "dt_internal.h"
 
 using namespace dt;
 
@@ -29,7 +29,7 @@ struct Profiler {
 const char *kClassName[KC_COUNT - KC_CONV_COUNT] = {
     "splitk_epilogue_kernel", "first_conv_kernel", "maxpool_kernel", "upcat_kernel", "head_kernel", "head_upsample_kernel",
     "time_bias_kernel", "cfg_update_kernel", "traj_metrics_kernel", "wasserstein_kernel", "resampled_distance_kernel",
-    "unet_fused_kernel", "pair_metrics_kernel"};
+    "unet_fused_kernel", "pair_metrics_kernel", "conv_strip_pair_bf16x6_kernel<256,128>"};
 // the printed name of a class: a convolution class is named after the form(s) that carry it (dt_conv_forms.h)
 const char *class_name(int cls) {
   switch (cls) {
@@ -38,7 +38,6 @@ const char *class_name(int cls) {
 #define DT_STRIP(c, kind, bm, bn, kc, wk) case c: return "conv_strip_bf16x6_kernel<" #bm "," #bn ">";
 #define DT_STRIPK(c, kind, bm, bn, kc, wk) case c: return "conv_strip_bf16x6_kernel<" #bm "," #bn ",K" #kc ">";
     DT_CONV_FORMS_FP32(DT_GEMM) DT_CONV_FORMS_BF16(DT_BF16) DT_CONV_FORMS_STRIP(DT_STRIP) DT_CONV_FORMS_STRIPK(DT_STRIPK)
-    case KC_CONVS_PAIR: return "conv_strip_pair_bf16x6_kernel<256,128>";   // (dt_conv_strip_pair.h)
     default: return kClassName[cls - KC_CONV_COUNT];
   }
 }
@@ -92,10 +91,10 @@ int dt_profile_end(void) {
   return DT_OK;
 }
 
-int dt_profile_class_count(void) { return KC_COUNT_ALL; }
+int dt_profile_class_count(void) { return KC_COUNT; }
 
 int dt_profile_read(int cls, const char **name, long long *launches, double *ms, double *flops, double *bytes) {
-  if (cls < 0 || cls >= KC_COUNT_ALL || !launches || !ms || !flops || !bytes) return DT_E_ARG;
+  if (cls < 0 || cls >= KC_COUNT || !launches || !ms || !flops || !bytes) return DT_E_ARG;
   if (name) *name = class_name(cls);
   *launches = 0; *ms = 0; *flops = 0; *bytes = 0;
   std::lock_guard<std::mutex> lock(g_prof.mu);

@@ -72,8 +72,8 @@ def test_dense64_kernels_do_not_spill():
 
 TILES = [(128, 128), (128, 64), (64, 128), (64, 64)]
 FORMS = ({f"conv_gemm_kernel<{bm},{bn}>" for bm, bn in TILES} | {f"conv_gemm_bf16x6_kernel<{bm},{bn}>" for bm, bn in TILES} |
-         {f"conv_strip_bf16x6_kernel<{bm},{bn},{kc},1>" for bm, bn in TILES + [(256, 64)] for kc in (1, 2)} |
-         {"conv_strip_bf16x6_kernel<64,128,2,2>", "conv_strip_bf16x6_kernel<128,64,2,2>", "conv_strip_bf16x6_kernel<64,64,4,4>"})
+         {f"conv_strip_bf16x6_kernel<{bm},{bn},{kc},1,1>" for bm, bn in TILES + [(256, 64)] for kc in (1, 2)} |
+         {"conv_strip_bf16x6_kernel<64,128,2,2,1>", "conv_strip_bf16x6_kernel<128,64,2,2,1>", "conv_strip_bf16x6_kernel<64,64,4,4,1>"})   # (<BM,BN,KC,WK,NH>)
 
 
 @pytest.mark.skipif(not _have_hipcc(), reason="hipcc is not installed")

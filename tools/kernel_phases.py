@@ -127,12 +127,14 @@ def format_report(rep):
 
 
 def parse_report(text):
-    """{kernel: counts} of a committed report (the inverse of format_report)"""
+    """{kernel: counts} of a committed report (the inverse of format_report).  The reports from before the strip kernel had
+    its NH parameter name it <BM,BN,KC,WK>: those are today's <BM,BN,KC,WK,1>."""
     out = {}
     for line in text.splitlines():
         parts = line.split()
         if len(parts) == 1 + len(FIELDS) and KERNELS.match(parts[0]):
-            out[parts[0]] = dict(zip(FIELDS, (int(v) for v in parts[1:])))
+            name = re.sub(r"^(conv_strip_bf16x6_kernel<\d+,\d+,\d+,\d+)>$", r"\1,1>", parts[0])
+            out[name] = dict(zip(FIELDS, (int(v) for v in parts[1:])))
     return out
 
 

@@ -75,9 +75,9 @@ def kernel_resources(source):
 
 
 def strip_template_args(name):
-    """(BM, BN, KC, WK) of a conv_strip_bf16x6_kernel<...> name, None for any other kernel"""
+    """(BM, BN, KC, WK) of a conv_strip_bf16x6_kernel<BM,BN,KC,WK[,NH]> name, None for any other kernel"""
     m = re.match(r"conv_strip_bf16x6_kernel<([\d,]+)>$", name)
-    return tuple(int(v) for v in m.group(1).split(",")) if m else None
+    return tuple(int(v) for v in m.group(1).split(","))[:4] if m else None
 
 
 def main(argv):
