@@ -86,6 +86,7 @@ struct dt_unet {
   int precision = DT_PREC_AUTO;   // DT_PREC_*: which convolution arithmetic the heuristic / autotuner may use
   bool head_fusion = true;   // dec1.conv2's epilogue evaluates the final 1x1 head (dt_unet_set_head_fusion)
   bool strip_pair = true;    // 256 x 64 K = 32 strip launches run the pair kernel where it serves them (dt_conv_strip_pair.h; DT_NO_STRIP_PAIR=1 at create time: off)
+  bool concat_in_place = true;   // decoder strip launches read the concat's skip half from the encoder's output (resolve_forward; test hook, DT_NO_CONCAT_IN_PLACE=1 at create time: off)
   dt::UnetGeom geo{};
   dt::BlockW blk[dt::kBlocks] = {};
   float *slab = nullptr;     // one device allocation holding every pointer of blk, tw and the head (SlabLayout)

@@ -177,6 +177,7 @@ int dt_unet_create(const dt_unet_desc *desc, const float *const *bt, const float
   if (!u) return (int)hipErrorOutOfMemory;
   u->geo = geo;
   u->strip_pair = getenv("DT_NO_STRIP_PAIR") == nullptr;
+  u->concat_in_place = getenv("DT_NO_CONCAT_IN_PLACE") == nullptr;
   const SlabLayout L = slab_layout(geo);
   DT_HIP_TRY(hipMalloc((void **)&u->slab, L.total * sizeof(float)));
   if (const int st = pack_slab(u.get(), L, bt, gt, s)) return st;
@@ -205,11 +206,16 @@ size_t dt_unet_workspace_bytes(const dt_unet *h, int batch_total, int H, int W) 
 int dt_unet_debug_activation(const dt_unet *h, int batch_total, int H, int W, int which, size_t *off, int *cp,
                              int *oh, int *ow) {
   if (!h || !off || !cp || !oh || !ow) return DT_E_NULL;
-  if (which < 0 || which > kBlocks) return DT_E_ARG;
+  if (which < 0 || which > kBlocks + 3) return DT_E_ARG;
   const FwdShape sh = FwdShape::rows_only(batch_total, H, W);
   if (const int bad = sh.validate()) return bad;
   const Plan pl = make_plan(h->geo, sh);
   if (which == kBlocks) { *off = pl.slab; *cp = 0; *oh = 0; *ow = 0; return DT_OK; }   // the split-K slab (diagnostics)
+  if (which > kBlocks) {   // the concat [upsampled | skip] that dec3 / dec2 / dec1 read
+    const int j = which - kBlocks + 4;
+    *off = pl.cat[j - 5]; *cp = h->geo.blk[j].cin_p; *oh = pl.H[j]; *ow = pl.W[j];
+    return DT_OK;
+  }
   *off = pl.o[which]; *cp = h->geo.blk[which].cout_p; *oh = pl.H[which]; *ow = pl.W[which];
   return DT_OK;
 }

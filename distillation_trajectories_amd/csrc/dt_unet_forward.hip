@@ -47,7 +47,8 @@ ResolvedForward resolve_forward(const dt_unet *u, const FwdShape &sh, const Tune
     f.pool_fused[j] = j <= 3 && h % 2 == 0 && w % 2 == 0 && (c2.splits > 1 || (w <= 16 && (w & (w - 1)) == 0));
     // a decoder block reads the concat [upsampled | skip]: when both of its readers are strip launches (conv1, and the 1x1 skip
     // folded into conv2) they fetch the skip half straight from the encoder's output and the concat holds the upsampled half only
-    f.concat_in_place[j] = j >= 5 && g.blk[j].has_res && is_strip(f.c[j][1].kind) && is_strip(c2.kind) && c2.fuse;
+    // (the handle's switch is a test hook: off, the same launches read the skip half from the concat buffer)
+    f.concat_in_place[j] = u->concat_in_place && j >= 5 && g.blk[j].has_res && is_strip(f.c[j][1].kind) && is_strip(c2.kind) && c2.fuse;
   }
   // dec1.conv2 also evaluates the final 1x1 head when its workgroups hold whole rows (one N tile, no split): the head is dec1's
   // only consumer, so dec1's own output is then never written

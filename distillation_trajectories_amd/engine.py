@@ -417,7 +417,8 @@ class UNetHandle:
         return eps
 
     def debug_activation(self, batch_total, H, W, which):
-        """NHWC view [Bt,h,w,cp] of block ``which``'s output inside the workspace of the last forward."""
+        """NHWC view [Bt,h,w,cp] of block ``which``'s output inside the workspace of the last forward (``which`` = 9, 10, 11: of
+        the concat [upsampled | skip] that dec3, dec2, dec1 read)."""
         off, cp, oh, ow = c_size_t(), c_int(), c_int(), c_int()
         check(self.lib.dt_unet_debug_activation(self.h, batch_total, H, W, which, ctypes.byref(off), ctypes.byref(cp),
                                                 ctypes.byref(oh), ctypes.byref(ow)), "dt_unet_debug_activation")

@@ -188,7 +188,10 @@ int dt_unet_set_fused(dt_unet *h, int on);
 int dt_unet_fused_active(const dt_unet *h, int H, int W);
 
 /* test hook: float offset / padded channel count of a block output inside the workspace
- * (which: 0..7 block outputs in DT order), valid after dt_unet_forward with the same shape */
+ * (which: 0..7 block outputs in DT order), valid after dt_unet_forward with the same shape.  which = 8: the split-K slab
+ * (offset only); which = 9, 10, 11: the concat [upsampled | skip] that dec3, dec2, dec1 read, channels_padded its padded
+ * input channels -- the skip half is left unwritten where both readers fetch it from the encoder's output
+ * (DT_NO_CONCAT_IN_PLACE=1 in the environment at create time, a test hook: it is always written and read there) */
 int dt_unet_debug_activation(const dt_unet *h, int batch_total, int H, int W, int which,
                              size_t *offset_floats, int *channels_padded, int *out_h, int *out_w);
 
