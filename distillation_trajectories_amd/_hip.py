@@ -184,6 +184,17 @@ RNG_SIGNATURES = {
                              c_longlong, c_longlong, c_longlong, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
+# name -> (restype, argtypes) of every symbol include/dt_hip_align.h declares (trajectory alignment: cost matrix, DTW, Frechet)
+_ALIGN_ROWS = [c_void_p, c_int, c_longlong, c_longlong, c_void_p, c_int, c_longlong, c_longlong, c_int, c_int]
+ALIGN_SIGNATURES = {
+    "dt_align_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "dt_align_min_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dt_align_cost": (c_int, _ALIGN_ROWS + [c_void_p, c_void_p, c_void_p]),
+    "dt_align_dp": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                            c_size_t, c_void_p]),
+    "dt_align": (c_int, _ALIGN_ROWS + [c_int, c_int] + [c_void_p] * 9 + [c_size_t, c_void_p]),
+}
+
 
 class TsneParams(ctypes.Structure):
     """dt_tsne_params of include/dt_hip_tsne.h"""
@@ -209,7 +220,7 @@ def load(path=None):
         raise HipLibraryError(f"cannot load {path}: {e}. There is no CPU fallback.") from e
     for name, (res, args) in {**SIGNATURES, **NOISE_SIGNATURES, **INCEPTION_SIGNATURES, **PCA_SIGNATURES,
                               **FID_SIGNATURES, **FID_COV_SIGNATURES, **LPIPS_SIGNATURES, **TSNE_SIGNATURES, **QUALITY_SIGNATURES,
-                              **QUALITY_STREAM_SIGNATURES, **EDIT_SIGNATURES, **RNG_SIGNATURES}.items():
+                              **QUALITY_STREAM_SIGNATURES, **EDIT_SIGNATURES, **RNG_SIGNATURES, **ALIGN_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

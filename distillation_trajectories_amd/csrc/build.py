@@ -12,7 +12,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["dt_conv.hip", "dt_conv_bf16.hip", "dt_conv_strip.hip", "dt_conv_strip_pair.hip", "dt_layers.hip", "dt_update.hip", "dt_metrics.hip", "dt_fused.hip", "dt_profile.hip", "dt_unet.hip",
-           "dt_unet_forward.hip", "dt_unet_tune.hip", "dt_sample.hip", "dt_featnet.hip", "dt_inception.hip", "dt_pca.hip", "dt_fid.hip", "dt_lpips.hip", "dt_tsne.hip", "dt_quality.hip", "dt_quality_stream.hip", "dt_edit.hip", "dt_rng.hip"]
+           "dt_unet_forward.hip", "dt_unet_tune.hip", "dt_sample.hip", "dt_featnet.hip", "dt_inception.hip", "dt_pca.hip", "dt_fid.hip", "dt_lpips.hip", "dt_tsne.hip", "dt_quality.hip", "dt_quality_stream.hip", "dt_edit.hip", "dt_rng.hip", "dt_align.hip"]
 HEADERS = ["dt_internal.h", "dt_conv_forms.h", "dt_conv_rows.h", "dt_batch.h", "dt_dense64.h", "dt_quality_math.h", "dt_featnet.h", "dt_conv_epilogue.h", "dt_conv_walk.h", "dt_conv_strip_kernel.h", "dt_conv_strip_pair.h", "dt_update_math.h", "dt_fused.h", "dt_unet.h", "dt_unet_layout.h", os.path.join("..", "..", "include", "dt_hip.h"),
            os.path.join("..", "..", "include", "dt_hip_noise.h"),
            os.path.join("..", "..", "include", "dt_hip_inception.h"),
@@ -24,7 +24,8 @@ HEADERS = ["dt_internal.h", "dt_conv_forms.h", "dt_conv_rows.h", "dt_batch.h", "
            os.path.join("..", "..", "include", "dt_hip_quality.h"),
            os.path.join("..", "..", "include", "dt_hip_quality_stream.h"),
            os.path.join("..", "..", "include", "dt_hip_edit.h"),
-           os.path.join("..", "..", "include", "dt_hip_rng.h")]
+           os.path.join("..", "..", "include", "dt_hip_rng.h"),
+           os.path.join("..", "..", "include", "dt_hip_align.h")]
 LIB = os.path.join(HERE, "libdt_hip.so")
 ARCH = "gfx950"
 
@@ -102,9 +103,10 @@ INCEPTION_SAN_DRIVER = os.path.join(OBJ_DIR, "dt_host_sanitize_inception")
 PCA_SAN_DRIVER = os.path.join(OBJ_DIR, "dt_host_sanitize_pca")
 FID_SAN_DRIVER = os.path.join(OBJ_DIR, "dt_host_sanitize_fid")
 LPIPS_SAN_DRIVER = os.path.join(OBJ_DIR, "dt_host_sanitize_lpips")
+ALIGN_SAN_DRIVER = os.path.join(OBJ_DIR, "dt_host_sanitize_align")
 
 
-def build_sanitizer_driver(verbose=False, driver="driver.cpp", out=SAN_DRIVER):
+def build_sanitizer_driver(verbose=False, driver="driver.cpp", out=SAN_DRIVER, sources=None):
     """tests/host_sanitize/<driver> + every library source, HOST code instrumented with AddressSanitizer and
     UndefinedBehaviorSanitizer (``-Xarch_host -fsanitize=...``; device code is left alone: GPU ASan is unavailable on this
     pool), one executable (default csrc/_build/dt_host_sanitize).  Cross-compiles without a GPU; tests/test_host_sanitize.py
@@ -113,12 +115,13 @@ def build_sanitizer_driver(verbose=False, driver="driver.cpp", out=SAN_DRIVER):
     os.makedirs(OBJ_DIR, exist_ok=True)
     root = os.path.dirname(os.path.dirname(HERE))
     driver = os.path.join(root, "tests", "host_sanitize", driver)
-    deps = [os.path.join(HERE, f) for f in SOURCES + HEADERS] + [driver, os.path.abspath(__file__)]
+    sources = SOURCES if sources is None else sources
+    deps = [os.path.join(HERE, f) for f in sources + HEADERS] + [driver, os.path.abspath(__file__)]
     if not _newer(out, deps):
         return out
     san = ["-Xarch_host", "-fsanitize=address", "-Xarch_host", "-fsanitize=undefined", "-Xarch_host", "-fno-omit-frame-pointer"]
     cmd = ([hipcc, f"--offload-arch={ARCH}", "-O1", "-g", "-std=c++17", "-Wno-unused-function", "-x", "hip"] + san +
-           [os.path.join(HERE, f) for f in SOURCES] + [driver, "-o", out])
+           [os.path.join(HERE, f) for f in sources] + [driver, "-o", out])
     if verbose:
         print(" ".join(cmd), flush=True)
     res = subprocess.run(cmd, capture_output=True, text=True)
@@ -158,6 +161,13 @@ def build_lpips_sanitizer_driver(verbose=False):
     return build_sanitizer_driver(verbose, driver="lpips_driver.cpp", out=LPIPS_SAN_DRIVER)
 
 
+def build_align_sanitizer_driver(verbose=False):
+    """tests/host_sanitize/align_driver.cpp with csrc/dt_align.hip alone, host code instrumented in the same way: the workspace
+    queries and argument errors of include/dt_hip_align.h, none of which reaches the GPU: csrc/_build/dt_host_sanitize_align
+    (run by tests/test_align_host.py, without a GPU)."""
+    return build_sanitizer_driver(verbose, driver="align_driver.cpp", out=ALIGN_SAN_DRIVER, sources=["dt_align.hip"])
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     if "--sanitize" in sys.argv:
@@ -167,3 +177,4 @@ if __name__ == "__main__":
         print(build_pca_sanitizer_driver(verbose=True))
         print(build_fid_sanitizer_driver(verbose=True))
         print(build_lpips_sanitizer_driver(verbose=True))
+        print(build_align_sanitizer_driver(verbose=True))

@@ -1140,6 +1140,157 @@ def device_tsne(a, b=None, perplexity=30.0, init=None, max_iter=1000, early_exag
     return out
 
 
+# ---------------------------------------------------------------------- trajectory alignment (include/dt_hip_align.h)
+ALIGN_MAX_N = 1024
+ALIGN_MAX_BAND = 1 << 20
+ALIGN_DTW, ALIGN_FRECHET = 0, 1
+ALIGN_OK, ALIGN_NONFINITE, ALIGN_NO_PATH = 0, 1, 2
+_ALIGN_KINDS = {"dtw": ("dtw",), "frechet": ("frechet",), "both": ("dtw", "frechet")}
+
+
+def _align_kinds(kind):
+    if kind not in _ALIGN_KINDS:
+        raise ValueError(f"kind={kind!r} must be one of {sorted(_ALIGN_KINDS)}")
+    return _ALIGN_KINDS[kind]
+
+
+def _align_band(band):
+    band = _count(band, "band")
+    if band > ALIGN_MAX_BAND:
+        raise ValueError(f"band={band} must be at most {ALIGN_MAX_BAND}")
+    return band
+
+
+def _align_rows(t, name, layout):
+    """[n, P, E] view of the rows of a trajectory tensor: step-major [n, S, ...] or, with layout "problem", [P, n, ...];
+    a 2-D [n, E] tensor is one problem.  Unit stride along E, a copy only where the tensor has none."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name} must be a torch tensor, got {type(t).__name__}")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{name} must be float32, got {t.dtype}")
+    if t.dim() < 2:
+        raise ValueError(f"{name} must be [n, E], step-major [n, S, ...] or [P, n, ...], got shape {tuple(t.shape)}")
+    if t.dim() == 2:
+        t = t.unsqueeze(1)
+    elif layout == "problem":
+        t = t.transpose(0, 1)
+    if t.dim() > 3:
+        t = t.flatten(2)
+    return t if t.stride(2) == 1 else t.contiguous()
+
+
+def _align_shape(n_a, n_b, P):
+    if not (2 <= n_a <= ALIGN_MAX_N and 2 <= n_b <= ALIGN_MAX_N):
+        raise ValueError(f"an alignment needs 2 <= n <= {ALIGN_MAX_N} states on both sides, got {n_a} and {n_b}")
+    if not 1 <= P <= 65535:
+        raise ValueError(f"unsupported number of problems P={P}")
+
+
+def _align_outputs(kinds, P, n_a, n_b, path, dev):
+    out = {"status": torch.empty(P, dtype=torch.int32, device=dev)}
+    for k in kinds:
+        out[k] = torch.empty(P, dtype=torch.float64, device=dev)
+        if path:
+            out[f"{k}_path"] = torch.empty(P, n_a + n_b - 1, 2, dtype=torch.int32, device=dev)
+            out[f"{k}_path_len"] = torch.empty(P, dtype=torch.int32, device=dev)
+    return out
+
+
+def device_align(X, Y, kind="both", band=0, path=True, cost=False, workspace_bytes=None, layout="step"):
+    """DTW and / or the discrete Fréchet distance between the trajectories X [nX, S, ...] and Y [nY, S, ...] (step-major
+    float32 device tensors, one problem per sample s, read in place; with ``layout="problem"`` [P, n, ...]): dt_align, the
+    fp64 matrix of Euclidean distances between every state of X and every state of Y, then one dynamic programme per kind.
+    ``kind``: "dtw", "frechet" or "both"; ``band``: 0, or a Sakoe-Chiba band in steps of the longer trajectory.
+    Returns device tensors {dtw, frechet [S] fp64, status [S] int32 (0 ok, 1 non-finite input: the values are NaN, 2 no
+    path)}, with ``path`` {dtw_path, frechet_path [S, nX+nY-1, 2] int32 (cells (i, j) from (0, 0), -1 past the length),
+    dtw_path_len, frechet_path_len [S] int32}, and with ``cost`` the matrices cost [S, nX, nY] fp64.
+    ``workspace_bytes``: a cap on the scratch; the problems then go through in chunks, with the same bits."""
+    kinds = _align_kinds(kind)
+    band = _align_band(band)
+    if layout not in ("step", "problem"):
+        raise ValueError(f"layout={layout!r} must be 'step' or 'problem'")
+    a, b = _align_rows(X, "X", layout), _align_rows(Y, "Y", layout)
+    (n_a, P, E), (n_b, Pb, Eb) = a.shape, b.shape
+    if (P, E) != (Pb, Eb):
+        raise ValueError(f"Y {tuple(Y.shape)} does not match X {tuple(X.shape)}: the same number of problems and the same "
+                         "state size are needed")
+    _align_shape(n_a, n_b, P)
+    if not 1 <= E <= 1 << 28:
+        raise ValueError(f"unsupported state size E={E}")
+    path, cost = bool(path), bool(cost)
+    lib = _hip.load()
+    least = lib.dt_align_min_workspace_bytes(n_a, n_b, int(path), int(cost))
+    ws_bytes = lib.dt_align_workspace_bytes(P, n_a, n_b, int(path), int(cost))
+    if workspace_bytes is not None:
+        if _count(workspace_bytes, "workspace_bytes") < least:
+            raise ValueError(f"workspace_bytes={workspace_bytes} is below one problem's {least} bytes")
+        ws_bytes = min(ws_bytes, int(workspace_bytes))
+    _require_cuda(a, "X")
+    _require_cuda(b, "Y")
+    dev = a.device
+    with torch.cuda.device(dev):
+        out = _align_outputs(kinds, P, n_a, n_b, path, dev)
+        if cost:
+            out["cost"] = torch.empty(P, n_a, n_b, dtype=torch.float64, device=dev)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        mask = sum(1 << (ALIGN_DTW if k == "dtw" else ALIGN_FRECHET) for k in kinds)
+        check(lib.dt_align(ptr(a), n_a, a.stride(1), a.stride(0), ptr(b), n_b, b.stride(1), b.stride(0), P, E, mask, band,
+                           ptr(out.get("cost")), ptr(out.get("dtw")), ptr(out.get("frechet")), ptr(out.get("dtw_path")),
+                           ptr(out.get("dtw_path_len")), ptr(out.get("frechet_path")), ptr(out.get("frechet_path_len")),
+                           ptr(out["status"]), ptr(ws), ws_bytes, stream_ptr()), "dt_align")
+    return out
+
+
+def device_align_cost_matrix(X, Y, layout="step"):
+    """The cost matrices alone (dt_align_cost): {cost [S, nX, nY] fp64, status [S] int32} for X and Y as in ``device_align``."""
+    if layout not in ("step", "problem"):
+        raise ValueError(f"layout={layout!r} must be 'step' or 'problem'")
+    a, b = _align_rows(X, "X", layout), _align_rows(Y, "Y", layout)
+    (n_a, P, E), (n_b, Pb, Eb) = a.shape, b.shape
+    if (P, E) != (Pb, Eb):
+        raise ValueError(f"Y {tuple(Y.shape)} does not match X {tuple(X.shape)}")
+    _align_shape(n_a, n_b, P)
+    if not 1 <= E <= 1 << 28:
+        raise ValueError(f"unsupported state size E={E}")
+    _require_cuda(a, "X")
+    _require_cuda(b, "Y")
+    lib = _hip.load()
+    with torch.cuda.device(a.device):
+        out = {"cost": torch.empty(P, n_a, n_b, dtype=torch.float64, device=a.device),
+               "status": torch.empty(P, dtype=torch.int32, device=a.device)}
+        check(lib.dt_align_cost(ptr(a), n_a, a.stride(1), a.stride(0), ptr(b), n_b, b.stride(1), b.stride(0), P, E,
+                                ptr(out["cost"]), ptr(out["status"]), stream_ptr()), "dt_align_cost")
+    return out
+
+
+def device_align_cost(cost, kind="both", band=0, path=True):
+    """The dynamic programmes of ``device_align`` on caller-made cost matrices [P, n_a, n_b] (or [n_a, n_b]) fp64 on the
+    device, for instance LPIPS between steps: dt_align_dp per kind.  The same outputs, without ``cost``; a NaN or Inf
+    entry gives status 1."""
+    kinds = _align_kinds(kind)
+    band = _align_band(band)
+    if not isinstance(cost, torch.Tensor) or cost.dtype != torch.float64 or cost.dim() not in (2, 3):
+        raise ValueError("cost must be a float64 tensor [P, n_a, n_b] or [n_a, n_b]")
+    if cost.dim() == 2:
+        cost = cost.unsqueeze(0)
+    P, n_a, n_b = cost.shape
+    _align_shape(n_a, n_b, P)
+    path = bool(path)
+    _require_cuda(cost, "cost")
+    lib = _hip.load()
+    cost = cost.contiguous()
+    dev = cost.device
+    with torch.cuda.device(dev):
+        out = _align_outputs(kinds, P, n_a, n_b, path, dev)
+        ws_bytes = lib.dt_align_workspace_bytes(P, n_a, n_b, int(path), 1)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        for k in kinds:
+            check(lib.dt_align_dp(ptr(cost), P, n_a, n_b, ALIGN_DTW if k == "dtw" else ALIGN_FRECHET, band, ptr(out[k]),
+                                  ptr(out.get(f"{k}_path")), ptr(out.get(f"{k}_path_len")), ptr(out["status"]), ptr(ws),
+                                  ws_bytes, stream_ptr()), "dt_align_dp")
+    return out
+
+
 # ---------------------------------------------------------------------- Fréchet distance (include/dt_hip_fid.h)
 FID_MAX_SIDE = 2048
 FID_MAX_ROWS = 32768
