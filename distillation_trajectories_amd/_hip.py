@@ -195,6 +195,17 @@ ALIGN_SIGNATURES = {
     "dt_align": (c_int, _ALIGN_ROWS + [c_int, c_int] + [c_void_p] * 9 + [c_size_t, c_void_p]),
 }
 
+# name -> (restype, argtypes) of every symbol include/dt_hip_cka.h declares (layer-wise CKA: centred Grams, the two estimators)
+_CKA_LAYERS = [POINTER(c_void_p), POINTER(c_longlong), POINTER(c_int), POINTER(c_int), POINTER(c_int), c_int]
+_CKA_GRAMS = [c_void_p, c_void_p, c_void_p]
+CKA_SIGNATURES = {
+    "dt_cka_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dt_cka_min_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "dt_cka_gram": (c_int, _CKA_LAYERS + [c_int] + _CKA_GRAMS + [c_void_p, c_size_t, c_void_p]),
+    "dt_cka_scores": (c_int, _CKA_GRAMS + [c_int] + _CKA_GRAMS + [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dt_cka": (c_int, (_CKA_LAYERS + _CKA_GRAMS) * 2 + [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+}
+
 
 class TsneParams(ctypes.Structure):
     """dt_tsne_params of include/dt_hip_tsne.h"""
@@ -220,7 +231,8 @@ def load(path=None):
         raise HipLibraryError(f"cannot load {path}: {e}. There is no CPU fallback.") from e
     for name, (res, args) in {**SIGNATURES, **NOISE_SIGNATURES, **INCEPTION_SIGNATURES, **PCA_SIGNATURES,
                               **FID_SIGNATURES, **FID_COV_SIGNATURES, **LPIPS_SIGNATURES, **TSNE_SIGNATURES, **QUALITY_SIGNATURES,
-                              **QUALITY_STREAM_SIGNATURES, **EDIT_SIGNATURES, **RNG_SIGNATURES, **ALIGN_SIGNATURES}.items():
+                              **QUALITY_STREAM_SIGNATURES, **EDIT_SIGNATURES, **RNG_SIGNATURES, **ALIGN_SIGNATURES,
+                              **CKA_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

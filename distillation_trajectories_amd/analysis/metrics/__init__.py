@@ -1,5 +1,7 @@
 """Set-level metrics of teacher and student samples (reference analysis/metrics/): FID (fid_score.py), LPIPS along the
 trajectories (perceptual.py) and KID, precision / recall, density / coverage (sample_quality.py), all on the device;
-and, beyond the reference, the alignment of a teacher's and a student's trajectory in time (alignment.py)."""
+and, beyond the reference, the alignment of a teacher's and a student's trajectory in time (alignment.py) and the
+layer-wise CKA of what their blocks represent (representation.py)."""
 from .alignment import align_trajectories, alignment_pairs, alignment_sweep
+from .representation import cka_layers, cka_sweep
 from .sample_quality import guidance_quality_sweep, quality_sweep

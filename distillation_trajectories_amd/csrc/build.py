@@ -12,7 +12,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["dt_conv.hip", "dt_conv_bf16.hip", "dt_conv_strip.hip", "dt_conv_strip_pair.hip", "dt_layers.hip", "dt_update.hip", "dt_metrics.hip", "dt_fused.hip", "dt_profile.hip", "dt_unet.hip",
-           "dt_unet_forward.hip", "dt_unet_tune.hip", "dt_sample.hip", "dt_featnet.hip", "dt_inception.hip", "dt_pca.hip", "dt_fid.hip", "dt_lpips.hip", "dt_tsne.hip", "dt_quality.hip", "dt_quality_stream.hip", "dt_edit.hip", "dt_rng.hip", "dt_align.hip"]
+           "dt_unet_forward.hip", "dt_unet_tune.hip", "dt_sample.hip", "dt_featnet.hip", "dt_inception.hip", "dt_pca.hip", "dt_fid.hip", "dt_lpips.hip", "dt_tsne.hip", "dt_quality.hip", "dt_quality_stream.hip", "dt_edit.hip", "dt_rng.hip", "dt_align.hip", "dt_cka.hip"]
 HEADERS = ["dt_internal.h", "dt_conv_forms.h", "dt_conv_rows.h", "dt_batch.h", "dt_dense64.h", "dt_quality_math.h", "dt_featnet.h", "dt_conv_epilogue.h", "dt_conv_walk.h", "dt_conv_strip_kernel.h", "dt_conv_strip_pair.h", "dt_update_math.h", "dt_fused.h", "dt_unet.h", "dt_unet_layout.h", os.path.join("..", "..", "include", "dt_hip.h"),
            os.path.join("..", "..", "include", "dt_hip_noise.h"),
            os.path.join("..", "..", "include", "dt_hip_inception.h"),
@@ -25,7 +25,8 @@ HEADERS = ["dt_internal.h", "dt_conv_forms.h", "dt_conv_rows.h", "dt_batch.h", "
            os.path.join("..", "..", "include", "dt_hip_quality_stream.h"),
            os.path.join("..", "..", "include", "dt_hip_edit.h"),
            os.path.join("..", "..", "include", "dt_hip_rng.h"),
-           os.path.join("..", "..", "include", "dt_hip_align.h")]
+           os.path.join("..", "..", "include", "dt_hip_align.h"),
+           os.path.join("..", "..", "include", "dt_hip_cka.h")]
 LIB = os.path.join(HERE, "libdt_hip.so")
 ARCH = "gfx950"
 
@@ -104,6 +105,7 @@ PCA_SAN_DRIVER = os.path.join(OBJ_DIR, "dt_host_sanitize_pca")
 FID_SAN_DRIVER = os.path.join(OBJ_DIR, "dt_host_sanitize_fid")
 LPIPS_SAN_DRIVER = os.path.join(OBJ_DIR, "dt_host_sanitize_lpips")
 ALIGN_SAN_DRIVER = os.path.join(OBJ_DIR, "dt_host_sanitize_align")
+CKA_SAN_DRIVER = os.path.join(OBJ_DIR, "dt_host_sanitize_cka")
 
 
 def build_sanitizer_driver(verbose=False, driver="driver.cpp", out=SAN_DRIVER, sources=None):
@@ -168,6 +170,13 @@ def build_align_sanitizer_driver(verbose=False):
     return build_sanitizer_driver(verbose, driver="align_driver.cpp", out=ALIGN_SAN_DRIVER, sources=["dt_align.hip"])
 
 
+def build_cka_sanitizer_driver(verbose=False):
+    """tests/host_sanitize/cka_driver.cpp with csrc/dt_cka.hip alone, host code instrumented in the same way: the workspace
+    arithmetic and argument errors of include/dt_hip_cka.h, none of which reaches the GPU: csrc/_build/dt_host_sanitize_cka
+    (run by tests/test_cka_host.py, without a GPU)."""
+    return build_sanitizer_driver(verbose, driver="cka_driver.cpp", out=CKA_SAN_DRIVER, sources=["dt_cka.hip"])
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     if "--sanitize" in sys.argv:
@@ -178,3 +187,4 @@ if __name__ == "__main__":
         print(build_fid_sanitizer_driver(verbose=True))
         print(build_lpips_sanitizer_driver(verbose=True))
         print(build_align_sanitizer_driver(verbose=True))
+        print(build_cka_sanitizer_driver(verbose=True))

@@ -171,6 +171,7 @@ class UNetHandle:
         self._consts = {}
         self._plans = {}              # (rows, H, W, images, single-pass images) -> plan id ("table:<sha1>", "tuned:<sha1>", "heuristic", "pinned")
         self._split = {}              # (rows, H, W) -> (images, single-pass images) last named for it: see shape()
+        self._head_fusion = True      # the library's switch as set_head_fusion left it (it has no getter)
         if not _FUSED_DEFAULT:
             self.set_fused(False)
 
@@ -240,6 +241,7 @@ class UNetHandle:
     def set_head_fusion(self, on):
         """Test hook (dt_unet_set_head_fusion): off = separate head launch, dec1's output is materialised."""
         check(self.lib.dt_unet_set_head_fusion(self.h, int(bool(on))), "dt_unet_set_head_fusion")
+        self._head_fusion = bool(on)
 
     @property
     def _tuned(self):
@@ -416,6 +418,34 @@ class UNetHandle:
         run()
         return eps
 
+    def block_features(self, x, tb, n_pass, tb_div, blocks=range(8)):
+        """The outputs of the residual blocks ``blocks`` (indices into BLOCK_NAMES: enc1..enc4, bottleneck, dec3..dec1) for
+        x [B, C, H, W], as ``PitchedFeatures`` over [n_pass * B, h, w, cp] views with the model's real channel counts: one
+        forward on the layered kernels with the head launched separately, so that every block output is stored (small
+        models that the fused kernel would serve included).  tb, n_pass and tb_div as in ``forward``.
+
+        The views ALIAS the handle's workspace: they hold until the handle's next forward or sampler call of this shape on
+        this stream; form the Grams (``device_cka_gram``) or copy (``.dense()``) before that.  The handle's head-fusion and
+        fused switches and its launch plans are as they were afterwards: a later ``forward`` gives the bits it gave before."""
+        _require_cuda(x, "x")
+        blocks = [int(j) for j in blocks]
+        if not blocks or any(not 0 <= j < _hip.N_BLOCKS for j in blocks):
+            raise ValueError(f"blocks must name some of the {_hip.N_BLOCKS} residual blocks, got {blocks}")
+        B, C, H, W = x.shape
+        if C != self.channels:
+            raise HipLibraryError(f"x has {C} channels, the model expects {self.channels}")
+        split = _Split(B, n_pass, 0, tb_div, False)
+        if self.shape(split.rows, H, W, B, 0) not in self._plans:
+            self._forward(x, tb, split)          # the shape's launch plan is settled as any other caller settles it
+        was = self._head_fusion
+        self.set_head_fusion(False)              # the fused whole-forward kernel needs the fused head: this selects the layered path
+        try:
+            self._forward(x, tb, split)
+        finally:
+            self.set_head_fusion(was)
+        real = [self.dims[0], self.dims[1], self.dims[2], self.dims[3], self.dims[3], self.dims[2], self.dims[1], self.dims[0]]
+        return [PitchedFeatures(self.debug_activation(split.rows, H, W, j), real[j]) for j in blocks]
+
     def debug_activation(self, batch_total, H, W, which):
         """NHWC view [Bt,h,w,cp] of block ``which``'s output inside the workspace of the last forward (``which`` = 9, 10, 11: of
         the concat [upsampled | skip] that dec3, dec2, dec1 read)."""
@@ -554,12 +584,11 @@ def cfg_update(rule, x, eps_u, eps_c, z, coef, has_noise, w=None, w_scalar=1.0, 
 
 
 # ---------------------------------------------------------------------- module-level forward
-def unet_forward_module(module, x, t, cond=None):
-    """General ``model(x, t, cond)`` (reference models.py:159-224): per-row t / cond with broadcasting."""
-    _require_cuda(x, "x")
-    h = UNetHandle.for_module(module)
-    B = x.shape[0]
-    t = t.reshape(t.shape[0], -1)[:, 0] if t.dim() > 1 else t
+def time_bias_rows(handle, B, t, cond=None):
+    """(tb, tb_div) of a forward of B images for ``model(x, t, cond)``'s arguments: t [B], [1] or a scalar, cond [B, 1], [1, 1]
+    or None, broadcast as the reference's forward does; one row shared by the batch when both are single."""
+    t = torch.as_tensor(t)
+    t = t.reshape(1) if t.dim() == 0 else (t.reshape(t.shape[0], -1)[:, 0] if t.dim() > 1 else t)
     rows = t.shape[0]
     c = None
     if cond is not None:
@@ -567,10 +596,17 @@ def unet_forward_module(module, x, t, cond=None):
         rows = max(rows, c.shape[0])
     if rows not in (1, B):
         raise RuntimeError(f"time/condition rows ({rows}) cannot broadcast onto batch {B}")
-    t_i = t.to(device=h.device, dtype=torch.int32).expand(rows).contiguous()
-    c_f = c.to(h.device).expand(rows).contiguous() if c is not None else None
-    tb = h.time_bias_general(t_i, c_f, None, rows)
-    return h.forward(x, tb, 1, B if rows == 1 else 1)
+    t_i = t.to(device=handle.device, dtype=torch.int32).expand(rows).contiguous()
+    c_f = c.to(handle.device).expand(rows).contiguous() if c is not None else None
+    return handle.time_bias_general(t_i, c_f, None, rows), (B if rows == 1 else 1)
+
+
+def unet_forward_module(module, x, t, cond=None):
+    """General ``model(x, t, cond)`` (reference models.py:159-224): per-row t / cond with broadcasting."""
+    _require_cuda(x, "x")
+    h = UNetHandle.for_module(module)
+    tb, tb_div = time_bias_rows(h, x.shape[0], t, cond)
+    return h.forward(x, tb, 1, tb_div)
 
 
 # ---------------------------------------------------------------------- metrics
@@ -1288,6 +1324,164 @@ def device_align_cost(cost, kind="both", band=0, path=True):
             check(lib.dt_align_dp(ptr(cost), P, n_a, n_b, ALIGN_DTW if k == "dtw" else ALIGN_FRECHET, band, ptr(out[k]),
                                   ptr(out.get(f"{k}_path")), ptr(out.get(f"{k}_path_len")), ptr(out["status"]), ptr(ws),
                                   ws_bytes, stream_ptr()), "dt_align_dp")
+    return out
+
+
+# ---------------------------------------------------------------------- layer-wise CKA (include/dt_hip_cka.h)
+CKA_MIN_N, CKA_MAX_N, CKA_MAX_LAYERS, CKA_MAX_P, CKA_SLAB = 4, 2048, 64, 1 << 24, 1024
+CKA_SUM_ROWS = 8
+CKA_SUMS = CKA_SUM_ROWS + CKA_MAX_N
+CKA_NONFINITE, CKA_ZERO_VARIANCE, CKA_SELF_NOT_POSITIVE = 1, 2, 4
+
+
+class PitchedFeatures:
+    """A layer of n feature rows inside a wider buffer: ``view`` [n, h, w, cp] float32 (NHWC, channels padded to cp, the
+    three inner axes dense, any row stride) of which the first ``c`` channels of every pixel are the features.  The pad
+    channels are never read.  ``UNetHandle.block_features`` returns these over the forward's workspace."""
+
+    def __init__(self, view, c):
+        if not isinstance(view, torch.Tensor) or view.dtype != torch.float32 or view.dim() != 4:
+            raise ValueError("PitchedFeatures: view must be a float32 tensor [n, h, w, cp]")
+        n, h, w, cp = view.shape
+        if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 1 <= c <= cp:
+            raise ValueError(f"PitchedFeatures: c={c!r} must be an int in [1, {cp}]")
+        if view.stride()[1:] != (w * cp, cp, 1):
+            raise ValueError(f"PitchedFeatures: the inner axes of view must be dense, got strides {view.stride()}")
+        self.view, self.c = view, int(c)
+
+    @property
+    def n(self):
+        return self.view.shape[0]
+
+    def dense(self):
+        """[n, h*w*c] copy without the pad channels (feature k = pixel * c + channel, the order the Gram walks)."""
+        return self.view[..., :self.c].reshape(self.n, -1)
+
+
+class CkaGrams(collections.namedtuple("CkaGrams", "gram sums status n")):
+    """``device_cka_gram``'s result, all on the device: gram [L, n, n] and sums [L, CKA_SUMS] float64, status [L] int32."""
+    __slots__ = ()
+
+
+def _cka_layers(layers, name):
+    """[(tensor kept alive, row stride, groups, c, pitch)] and n of a list of layers, each checked"""
+    if isinstance(layers, (torch.Tensor, PitchedFeatures)):
+        layers = [layers]
+    try:
+        layers = list(layers)
+    except TypeError:
+        raise ValueError(f"{name} must be a list of layers") from None
+    if not 1 <= len(layers) <= CKA_MAX_LAYERS:
+        raise ValueError(f"{name} must hold 1 .. {CKA_MAX_LAYERS} layers, got {len(layers)}")
+    out, n = [], None
+    for i, layer in enumerate(layers):
+        if isinstance(layer, PitchedFeatures):
+            v = layer.view
+            desc = (v, v.stride(0), v.shape[1] * v.shape[2], layer.c, v.shape[3])
+        elif isinstance(layer, torch.Tensor):
+            if layer.dtype != torch.float32 or layer.dim() < 2:
+                raise ValueError(f"{name}[{i}] must be a float32 tensor [n, ...], got {tuple(layer.shape)} {layer.dtype}")
+            v = layer.flatten(1)
+            if v.shape[1] > 1 and v.stride(1) != 1:
+                v = v.contiguous()
+            desc = (v, v.stride(0), 1, v.shape[1], v.shape[1])
+        else:
+            raise ValueError(f"{name}[{i}] must be a torch tensor or PitchedFeatures, got {type(layer).__name__}")
+        if not 1 <= desc[2] * desc[3] <= CKA_MAX_P:
+            raise ValueError(f"{name}[{i}] has {desc[2] * desc[3]} features, 1 .. {CKA_MAX_P} are supported")
+        if desc[1] < 0:
+            raise ValueError(f"{name}[{i}] has a negative row stride")
+        if n is None:
+            n = v.shape[0]
+        elif v.shape[0] != n:
+            raise ValueError(f"{name}[{i}] has {v.shape[0]} rows, the layers before it {n}: CKA compares the same inputs")
+        out.append(desc)
+    if not CKA_MIN_N <= n <= CKA_MAX_N:
+        raise ValueError(f"CKA needs {CKA_MIN_N} <= n <= {CKA_MAX_N} rows, got {n}")
+    return out, n
+
+
+def _cka_workspace_bytes(workspace_bytes):
+    return None if workspace_bytes is None else _count(workspace_bytes, "workspace_bytes")
+
+
+def device_cka_gram(layers, workspace_bytes=None):
+    """Feature-centred fp64 Grams of a list of layers over the same n inputs (dt_cka_gram).  A layer is a float32 device
+    tensor [n, ...] (trailing axes flattened, row stride honoured, no copy where the trailing axes are dense) or a
+    ``PitchedFeatures``.  Returns ``CkaGrams`` (gram, sums, status, n), all on the device.  ``workspace_bytes``: a cap on
+    the scratch; a layer's slabs then take turns, with the same bits."""
+    descs, n = _cka_layers(layers, "layers")
+    cap = _cka_workspace_bytes(workspace_bytes)
+    L, p_max = len(descs), max(d[2] * d[3] for d in descs)
+    lib = _hip.load()
+    ws_bytes = lib.dt_cka_workspace_bytes(L, n, p_max)
+    if cap is not None:
+        least = lib.dt_cka_min_workspace_bytes(n, p_max)
+        if cap < least:
+            raise ValueError(f"workspace_bytes={cap} is below the {least} bytes that the means and one slab take")
+        ws_bytes = min(ws_bytes, cap)
+    for d in descs:
+        _require_cuda(d[0], "a CKA layer")
+    dev = descs[0][0].device
+    if any(d[0].device != dev for d in descs):
+        raise ValueError("the layers must live on one device")
+    base = (c_void_p * L)(*[d[0].data_ptr() for d in descs])
+    rs = (ctypes.c_longlong * L)(*[d[1] for d in descs])
+    groups, c, pitch = ((c_int * L)(*[d[k] for d in descs]) for k in (2, 3, 4))
+    with torch.cuda.device(dev):
+        out = CkaGrams(torch.empty(L, n, n, dtype=torch.float64, device=dev),
+                       torch.empty(L, CKA_SUMS, dtype=torch.float64, device=dev),
+                       torch.empty(L, dtype=torch.int32, device=dev), n)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        check(lib.dt_cka_gram(base, rs, groups, c, pitch, L, n, ptr(out.gram), ptr(out.sums), ptr(out.status), ptr(ws),
+                              ws_bytes, stream_ptr()), "dt_cka_gram")
+    return out
+
+
+def _cka_grams_check(g, name):
+    L = g.gram.shape[0] if isinstance(g.gram, torch.Tensor) and g.gram.dim() == 3 else -1
+    ok = (L >= 1 and g.gram.dtype == torch.float64 and tuple(g.gram.shape) == (L, g.n, g.n) and g.gram.is_contiguous()
+          and isinstance(g.sums, torch.Tensor) and g.sums.dtype == torch.float64 and tuple(g.sums.shape) == (L, CKA_SUMS)
+          and g.sums.is_contiguous() and isinstance(g.status, torch.Tensor) and g.status.dtype == torch.int32
+          and tuple(g.status.shape) == (L,))
+    if not ok or not 1 <= L <= CKA_MAX_LAYERS or not CKA_MIN_N <= g.n <= CKA_MAX_N:
+        raise ValueError(f"{name} is not a CkaGrams of device_cka_gram")
+
+
+def device_cka(a, b=None, workspace_bytes=None):
+    """Linear CKA, biased and debiased, between every layer of ``a`` and every layer of ``b`` (``b=None``: of ``a``
+    itself).  ``a`` and ``b`` are lists of layers as ``device_cka_gram`` takes them, or its ``CkaGrams`` results, so that
+    one side's Grams are made once and scored many times.  Returns device tensors {cka, cka_unbiased [La, Lb] float64,
+    hsic [La, Lb, 2] float64 (the two numerators), status_a [La], status_b [Lb] int32 (bits CKA_NONFINITE,
+    CKA_ZERO_VARIANCE, CKA_SELF_NOT_POSITIVE; a score that involves a flagged layer is NaN for the estimator concerned)}.
+    The contract is in include/dt_hip_cka.h."""
+    sides = []
+    for side, name in ((a, "a"), (b, "b")):
+        if side is None and name == "b":
+            sides.append(None)
+        elif isinstance(side, CkaGrams):
+            _cka_grams_check(side, name)
+            sides.append(side)
+        else:
+            sides.append(_cka_layers(side, name))
+    n = [s.n if isinstance(s, CkaGrams) else s[1] for s in sides if s is not None]
+    if len(set(n)) != 1:
+        raise ValueError(f"a has {n[0]} rows and b {n[1]}: CKA compares features of the same inputs")
+    _cka_workspace_bytes(workspace_bytes)
+    ga = a if isinstance(a, CkaGrams) else device_cka_gram(a, workspace_bytes)
+    gb = ga if b is None else (b if isinstance(b, CkaGrams) else device_cka_gram(b, workspace_bytes))
+    for g in (ga, gb):
+        _require_cuda(g.gram, "a CKA Gram")
+    if gb.gram.device != ga.gram.device:
+        raise ValueError("a and b must live on one device")
+    La, Lb, dev = ga.gram.shape[0], gb.gram.shape[0], ga.gram.device
+    with torch.cuda.device(dev):
+        out = {"cka": torch.empty(La, Lb, dtype=torch.float64, device=dev),
+               "cka_unbiased": torch.empty(La, Lb, dtype=torch.float64, device=dev),
+               "hsic": torch.empty(La, Lb, 2, dtype=torch.float64, device=dev), "status_a": ga.status, "status_b": gb.status}
+        check(_hip.load().dt_cka_scores(ptr(ga.gram), ptr(ga.sums), ptr(ga.status), La, ptr(gb.gram), ptr(gb.sums),
+                                        ptr(gb.status), Lb, n[0], ptr(out["cka"]), ptr(out["cka_unbiased"]), ptr(out["hsic"]),
+                                        stream_ptr()), "dt_cka_scores")
     return out
 
 
