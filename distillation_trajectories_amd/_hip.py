@@ -206,6 +206,16 @@ CKA_SIGNATURES = {
     "dt_cka": (c_int, (_CKA_LAYERS + _CKA_GRAMS) * 2 + [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
+# name -> (restype, argtypes) of every symbol include/dt_hip_spectral.h declares (spatial-frequency spectra of the states)
+_SPECTRAL_ROWS = [c_void_p, c_longlong, c_longlong]
+_SPECTRAL_TAIL = [c_int] * 5 + [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+SPECTRAL_SIGNATURES = {
+    "dt_spectral_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dt_spectral_power": (c_int, _SPECTRAL_ROWS + _SPECTRAL_TAIL),
+    "dt_spectral_pair": (c_int, _SPECTRAL_ROWS * 2 + _SPECTRAL_TAIL),
+    "dt_spectral_sum": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_void_p]),
+}
+
 
 class TsneParams(ctypes.Structure):
     """dt_tsne_params of include/dt_hip_tsne.h"""
@@ -232,7 +242,7 @@ def load(path=None):
     for name, (res, args) in {**SIGNATURES, **NOISE_SIGNATURES, **INCEPTION_SIGNATURES, **PCA_SIGNATURES,
                               **FID_SIGNATURES, **FID_COV_SIGNATURES, **LPIPS_SIGNATURES, **TSNE_SIGNATURES, **QUALITY_SIGNATURES,
                               **QUALITY_STREAM_SIGNATURES, **EDIT_SIGNATURES, **RNG_SIGNATURES, **ALIGN_SIGNATURES,
-                              **CKA_SIGNATURES}.items():
+                              **CKA_SIGNATURES, **SPECTRAL_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

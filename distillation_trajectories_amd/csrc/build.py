@@ -12,7 +12,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["dt_conv.hip", "dt_conv_bf16.hip", "dt_conv_strip.hip", "dt_conv_strip_pair.hip", "dt_layers.hip", "dt_update.hip", "dt_metrics.hip", "dt_fused.hip", "dt_profile.hip", "dt_unet.hip",
-           "dt_unet_forward.hip", "dt_unet_tune.hip", "dt_sample.hip", "dt_featnet.hip", "dt_inception.hip", "dt_pca.hip", "dt_fid.hip", "dt_lpips.hip", "dt_tsne.hip", "dt_quality.hip", "dt_quality_stream.hip", "dt_edit.hip", "dt_rng.hip", "dt_align.hip", "dt_cka.hip"]
+           "dt_unet_forward.hip", "dt_unet_tune.hip", "dt_sample.hip", "dt_featnet.hip", "dt_inception.hip", "dt_pca.hip", "dt_fid.hip", "dt_lpips.hip", "dt_tsne.hip", "dt_quality.hip", "dt_quality_stream.hip", "dt_edit.hip", "dt_rng.hip", "dt_align.hip", "dt_cka.hip", "dt_spectral.hip"]
 HEADERS = ["dt_internal.h", "dt_conv_forms.h", "dt_conv_rows.h", "dt_batch.h", "dt_dense64.h", "dt_quality_math.h", "dt_featnet.h", "dt_conv_epilogue.h", "dt_conv_walk.h", "dt_conv_strip_kernel.h", "dt_conv_strip_pair.h", "dt_update_math.h", "dt_fused.h", "dt_unet.h", "dt_unet_layout.h", os.path.join("..", "..", "include", "dt_hip.h"),
            os.path.join("..", "..", "include", "dt_hip_noise.h"),
            os.path.join("..", "..", "include", "dt_hip_inception.h"),
@@ -26,7 +26,8 @@ HEADERS = ["dt_internal.h", "dt_conv_forms.h", "dt_conv_rows.h", "dt_batch.h", "
            os.path.join("..", "..", "include", "dt_hip_edit.h"),
            os.path.join("..", "..", "include", "dt_hip_rng.h"),
            os.path.join("..", "..", "include", "dt_hip_align.h"),
-           os.path.join("..", "..", "include", "dt_hip_cka.h")]
+           os.path.join("..", "..", "include", "dt_hip_cka.h"),
+           os.path.join("..", "..", "include", "dt_hip_spectral.h")]
 LIB = os.path.join(HERE, "libdt_hip.so")
 ARCH = "gfx950"
 
@@ -106,6 +107,7 @@ FID_SAN_DRIVER = os.path.join(OBJ_DIR, "dt_host_sanitize_fid")
 LPIPS_SAN_DRIVER = os.path.join(OBJ_DIR, "dt_host_sanitize_lpips")
 ALIGN_SAN_DRIVER = os.path.join(OBJ_DIR, "dt_host_sanitize_align")
 CKA_SAN_DRIVER = os.path.join(OBJ_DIR, "dt_host_sanitize_cka")
+SPECTRAL_SAN_DRIVER = os.path.join(OBJ_DIR, "dt_host_sanitize_spectral")
 
 
 def build_sanitizer_driver(verbose=False, driver="driver.cpp", out=SAN_DRIVER, sources=None):
@@ -177,6 +179,14 @@ def build_cka_sanitizer_driver(verbose=False):
     return build_sanitizer_driver(verbose, driver="cka_driver.cpp", out=CKA_SAN_DRIVER, sources=["dt_cka.hip"])
 
 
+def build_spectral_sanitizer_driver(verbose=False):
+    """tests/host_sanitize/spectral_driver.cpp with csrc/dt_spectral.hip (and csrc/dt_profile.hip, whose ProfileScope it opens),
+    host code instrumented in the same way: the workspace query and argument errors of include/dt_hip_spectral.h, none of
+    which reaches the GPU: csrc/_build/dt_host_sanitize_spectral (run by tests/test_spectral_host.py, without a GPU)."""
+    return build_sanitizer_driver(verbose, driver="spectral_driver.cpp", out=SPECTRAL_SAN_DRIVER,
+                                  sources=["dt_spectral.hip", "dt_profile.hip"])
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     if "--sanitize" in sys.argv:
@@ -188,3 +198,4 @@ if __name__ == "__main__":
         print(build_lpips_sanitizer_driver(verbose=True))
         print(build_align_sanitizer_driver(verbose=True))
         print(build_cka_sanitizer_driver(verbose=True))
+        print(build_spectral_sanitizer_driver(verbose=True))

@@ -59,6 +59,7 @@ enum KernelClass {   // the convolution classes come first: ConvClass (dt_conv_f
   KC_SPLITK_EPILOGUE = KC_CONV_COUNT, KC_FIRST_CONV, KC_POOL, KC_UPCAT, KC_HEAD, KC_HEAD_UP, KC_TIME_BIAS, KC_UPDATE, KC_METRICS,
   KC_WASSERSTEIN, KC_RESAMPLE, KC_FUSED, KC_PAIR_METRICS,
   KC_CONVS_PAIR,     // launches that the strip kernel's NH = 2 form serves (dt_conv_strip_pair.h): not a ConvClass, it has no form row
+  KC_SPECTRAL,       // the spectra of dt_spectral.hip: table sort, transform and binning, sample sums
   KC_COUNT
 };
 struct ProfileScope {

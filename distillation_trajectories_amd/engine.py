@@ -1485,6 +1485,164 @@ def device_cka(a, b=None, workspace_bytes=None):
     return out
 
 
+# ---------------------------------------------------------------------- spatial-frequency spectra (include/dt_hip_spectral.h)
+SPECTRAL_MAX_HW, SPECTRAL_MAX_C, SPECTRAL_MAX_BINS, SPECTRAL_MAX_ROWS = 64, 64, 256, 1 << 24
+SPECTRAL_PAIR_K = 5
+SPECTRAL_PA, SPECTRAL_PB, SPECTRAL_CRE, SPECTRAL_CIM, SPECTRAL_D = range(5)
+SPECTRAL_OK, SPECTRAL_NONFINITE = 0, 1
+_RADIAL_TABLES = {}
+
+
+def _spectral_picture(C, H, W):
+    C, H, W = _count(C, "C", 1), _count(H, "H", 1), _count(W, "W", 1)
+    if C > SPECTRAL_MAX_C or H > SPECTRAL_MAX_HW or W > SPECTRAL_MAX_HW:
+        raise ValueError(f"a spectrum takes C <= {SPECTRAL_MAX_C} and H, W <= {SPECTRAL_MAX_HW}, got C={C}, H={H}, W={W}")
+    return C, H, W
+
+
+def radial_bins(H, W):
+    """(table int32 [H, W], cells_per_bin int64 [n_bins]) of the radial binning of an H x W spectrum.  Coefficient (u, v)
+    has the signed frequencies fu = min(u, H - u), fv = min(v, W - v) and the radius r, in cycles per max(H, W) pixels,
+    r^2 = (fu M / H)^2 + (fv M / W)^2 with M = max(H, W); its bin is round(r) (halves up), decided in integers:
+    bin = #{b >= 0 : (2b + 1)^2 (HW)^2 <= 4 r^2 (HW)^2}, so that no table depends on libm.  DC is alone in bin 0, the table
+    is symmetric under (u, v) -> (-u, -v), and n_bins = max bin + 1."""
+    _, H, W = _spectral_picture(1, H, W)
+    M = max(H, W)
+    fu = np.minimum(np.arange(H), H - np.arange(H)).astype(np.int64)
+    fv = np.minimum(np.arange(W), W - np.arange(W)).astype(np.int64)
+    q = 4 * ((fu[:, None] * M * W) ** 2 + (fv[None, :] * M * H) ** 2)       # 4 r^2 (HW)^2 < 2^40
+    table = np.zeros((H, W), dtype=np.int64)
+    b = 0
+    while True:
+        above = q >= (2 * b + 1) ** 2 * (H * W) ** 2
+        if not above.any():
+            break
+        table += above
+        b += 1
+    return table.astype(np.int32), np.bincount(table.ravel())
+
+
+def _spectral_bins(bins, H, W):
+    """``bins`` as a host table int32 [H, W] and its n_bins, checked (None: None, the radial table)"""
+    if bins is None:
+        return None
+    host = bins.detach().cpu().numpy() if isinstance(bins, torch.Tensor) else np.asarray(bins)
+    if host.shape != (H, W):
+        raise ValueError(f"bins must be a table [H, W] = [{H}, {W}], got shape {tuple(host.shape)}")
+    if host.dtype.kind not in "iu":
+        raise ValueError(f"bins must hold integers, got {host.dtype}")
+    low, high = int(host.min()), int(host.max())
+    if low < -1 or high < 0 or high >= SPECTRAL_MAX_BINS:
+        raise ValueError(f"bins must hold -1 (left out) or a bin in [0, {SPECTRAL_MAX_BINS}) and name at least one bin, "
+                         f"got values in [{low}, {high}]")
+    return np.ascontiguousarray(host.astype(np.int32)), high + 1
+
+
+def _spectral_table(bins, H, W, device):
+    """(device table int32 [H, W], n_bins) of what ``_spectral_bins`` returned (the radial table is kept per shape and device)"""
+    if bins is not None:
+        return torch.from_numpy(bins[0]).to(device), bins[1]
+    key = (H, W, str(device))
+    if key not in _RADIAL_TABLES:
+        table, cells = radial_bins(H, W)
+        _RADIAL_TABLES[key] = (torch.from_numpy(table).to(device), len(cells))
+    return _RADIAL_TABLES[key]
+
+
+def _spectral_rows(t, name, E):
+    """(tensor, leading shape, n_outer, n_inner, outer stride, inner stride) of a set of rows of E floats: [n, S, E]
+    (contiguous or a view: a slice of the sample axis, every k-th state) or flat [Q, E]; read in place when the rows
+    themselves are contiguous, copied otherwise"""
+    t = _f32_rows(t, name, "[n, S, E] or [Q, E]")
+    if t.shape[-1] != E:
+        raise ValueError(f"{name} has rows of {t.shape[-1]} floats, C*H*W = {E} are needed")
+    if t.numel() == 0 or t.numel() // E > SPECTRAL_MAX_ROWS:
+        raise ValueError(f"{name} must hold between 1 and {SPECTRAL_MAX_ROWS} rows, got shape {tuple(t.shape)}")
+    if E > 1 and t.stride(-1) != 1:
+        t = t.contiguous()
+    if t.dim() == 2:
+        return t, (t.shape[0],), 1, t.shape[0], 0, t.stride(0)
+    return t, tuple(t.shape[:2]), t.shape[0], t.shape[1], t.stride(0), t.stride(1)
+
+
+def _spectral_sum(lib, out, status, n_outer, n_inner, C, n_bins, K):
+    sums = torch.empty(n_outer, C, n_bins, K, dtype=torch.float64, device=out.device)
+    count = torch.empty(n_outer, dtype=torch.int32, device=out.device)
+    check(lib.dt_spectral_sum(ptr(out), ptr(status), n_outer, n_inner, C, n_bins, K, ptr(sums), ptr(count), stream_ptr()),
+          "dt_spectral_sum")
+    return sums, count
+
+
+def device_spectrum(X, C, H, W, bins=None, sum_samples=False, workspace_bytes=None):
+    """Per-band power spectrum of the pictures of X: [n, S, E] (a trajectory or a view of one) or [Q, E], float32 on the
+    device, E = C*H*W in NCHW order, read in place (dt_spectral_power: the unnormalised fp64 DFT of every channel, |F|^2
+    summed over the cells of each bin).  ``bins``: an integer table [H, W] of bin numbers, -1 for a coefficient that is
+    left out; None: ``radial_bins(H, W)``.  Returns device tensors {power [.., C, n_bins] fp64, status [..] int32 (0 ok,
+    1 a NaN or Inf in the row: its outputs are NaN)}, [..] being [n, S] or [Q]; with ``sum_samples`` power is
+    [n, C, n_bins] (or [C, n_bins]), summed over the samples in index order without the flagged rows, and count [n] (or
+    a scalar) says how many were added.  ``workspace_bytes``: a larger scratch than needed; it changes nothing."""
+    return _spectral_call(X, None, C, H, W, bins, sum_samples, workspace_bytes)
+
+
+def device_spectral_pair(X, Y, C, H, W, bins=None, sum_samples=False, workspace_bytes=None):
+    """Per-band spectra of a teacher set X against a student set Y of the same shape (each as in ``device_spectrum``, with
+    strides of its own): dt_spectral_pair.  With A = DFT(x), B = DFT(y) and Delta = DFT(double(x) - double(y)) per
+    channel, returns device tensors {power_a = sum |A|^2, power_b = sum |B|^2, error = sum |Delta|^2 [.., C, n_bins],
+    cross [.., C, n_bins, 2] = sum A conj(B) (real, imaginary), status [..]}, all fp64 sums over the cells of a bin;
+    ``sum_samples`` as in ``device_spectrum``, with count."""
+    if Y is None:
+        raise ValueError("Y must be a torch tensor, got None")
+    return _spectral_call(X, Y, C, H, W, bins, sum_samples, workspace_bytes)
+
+
+def _spectral_call(X, Y, C, H, W, bins, sum_samples, workspace_bytes):
+    C, H, W = _spectral_picture(C, H, W)
+    E = C * H * W
+    bins = _spectral_bins(bins, H, W)
+    if workspace_bytes is not None:
+        _count(workspace_bytes, "workspace_bytes")
+    a, lead, n_outer, n_inner, a_os, a_is = _spectral_rows(X, "X", E)
+    pair = Y is not None
+    if pair:
+        b, lead_b, _, _, b_os, b_is = _spectral_rows(Y, "Y", E)
+        if lead_b != lead:
+            raise ValueError(f"Y {tuple(Y.shape)} does not match X {tuple(X.shape)}")
+    for t, name in ((a, "X"), (b, "Y")) if pair else ((a, "X"),):
+        if not t.is_cuda:
+            raise ValueError(f"{name} must be on the device, got {t.device}: the MI355X path has no CPU fallback")
+    if pair and b.device != a.device:
+        raise ValueError(f"X is on {a.device}, Y on {b.device}")
+    dev = a.device
+    with torch.cuda.device(dev):
+        table, n_bins = _spectral_table(bins, H, W, dev)
+        lib = _hip.load()
+        need = lib.dt_spectral_workspace_bytes(H, W, n_bins)
+        if workspace_bytes is not None and workspace_bytes < need:
+            raise ValueError(f"workspace_bytes={workspace_bytes} is below the {need} bytes a {H} x {W} table needs")
+        ws_bytes = need if workspace_bytes is None else int(workspace_bytes)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        rows, K = n_outer * n_inner, SPECTRAL_PAIR_K if pair else 1
+        out = torch.empty(rows, C, n_bins, K, dtype=torch.float64, device=dev)
+        status = torch.empty(rows, dtype=torch.int32, device=dev)
+        tail = (n_outer, n_inner, C, H, W, ptr(table), n_bins, ptr(out), ptr(status), ptr(ws), ws_bytes, stream_ptr())
+        if pair:
+            check(lib.dt_spectral_pair(ptr(a), a_os, a_is, ptr(b), b_os, b_is, *tail), "dt_spectral_pair")
+        else:
+            check(lib.dt_spectral_power(ptr(a), a_os, a_is, *tail), "dt_spectral_power")
+        res = {"status": status.view(lead)}
+        if sum_samples:
+            out, count = _spectral_sum(lib, out, status, n_outer, n_inner, C, n_bins, K)
+            lead = lead[:-1]
+            res["count"] = count.view(lead)
+        v = out.view(lead + (C, n_bins, K))
+        if pair:
+            res.update(power_a=v[..., SPECTRAL_PA], power_b=v[..., SPECTRAL_PB], cross=v[..., SPECTRAL_CRE:SPECTRAL_CIM + 1],
+                       error=v[..., SPECTRAL_D])
+        else:
+            res["power"] = v[..., 0]
+    return res
+
+
 # ---------------------------------------------------------------------- Fréchet distance (include/dt_hip_fid.h)
 FID_MAX_SIDE = 2048
 FID_MAX_ROWS = 32768
