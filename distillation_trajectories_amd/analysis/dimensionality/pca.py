@@ -4,6 +4,11 @@ The result is that of ``sklearn.decomposition.PCA(n_components=k, svd_solver="fu
 rows: column mean, singular values, explained variance and ratio, components with svd_flip's sign rule, scores.  The
 reference's callers run sklearn's default solver, which is randomized for these shapes and takes no random_state, so its
 own numbers change from run to run (tests/test_pca_host.py records by how much).
+
+Two places where the answer is not sklearn's vector for vector (include/dt_hip_pca.h): inside a repeated eigenvalue the
+components are some orthonormal basis of the same subspace, and a direction without variance (a rank below
+``n_components``) is reported as zeros (singular value, variances, component, scores) where sklearn returns an arbitrary
+unit vector.
 """
 import warnings
 

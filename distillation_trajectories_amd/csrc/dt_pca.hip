@@ -11,7 +11,8 @@
 //      symmetric rank-2 update per column, each a launch spread over the chip (the n x n fp64 matrix lives in the
 //      workspace: it does not fit in LDS from n ~ 140 up); then, one workgroup per problem (pca_eigen_kernel), bisection
 //      with Sturm counts for the k largest eigenvalues, inverse iteration for their vectors (dstein-like: clusters
-//      re-orthogonalised) and the back-transformation through the stored reflectors;
+//      re-orthogonalised) and the back-transformation through the stored reflectors; a lambda_j within n eps ||T|| of
+//      zero is a null direction and is set to 0 there, which makes stage 4 write zeros for it;
 //   4. components v = Xc^T u / s (pca_components_kernel), then the sign rule of sklearn's svd_flip(u_based_decision=False),
 //      scores s * u and the variances (pca_finish_kernel).
 #include <float.h>
@@ -199,6 +200,12 @@ __global__ __launch_bounds__(kThreads) void pca_eigen_kernel(int n, int E, int k
   }
   __syncthreads();
 
+  // Null directions.  This stage resolves lambda no finer than the n eps ||T|| it widens its own Gershgorin interval by: a
+  // lambda_j at or below that is rounding noise of either sign, and its sign must not decide the output.  lambda_j = 0
+  // makes the components and the finish kernel write zeros for the direction (singular value, variance, ratio, component,
+  // score column), as DT_PCA_ZERO_VARIANCE does for a whole problem.
+  if (t < k && lam[t] <= n * DBL_EPSILON * tnorm) lam[t] = 0.0;
+
   // back-transformation u = H_0 ... H_{n-3} z: one wave per vector; lane l owns rows r = l (mod 64) throughout
   const int w = t / 64, lane = t % 64;
   const double *tau = base + L.tau;
@@ -308,7 +315,7 @@ __global__ __launch_bounds__(kThreads) void pca_finish_kernel(int n, int E, int 
     for (int e = t; e < E; e += kThreads) comp[(size_t)j * E + e] = (float)(sign * V[e]);
     const double lj = fmax(base[L.lam + j], 0.0), s = sqrt(lj);
     const double *u = base + L.Z + (size_t)j * n;
-    for (int i = t; i < n; i += kThreads) scores[(size_t)i * k + j] = (float)(sign * s * u[i]);
+    for (int i = t; i < n; i += kThreads) scores[(size_t)i * k + j] = s > 0.0 ? (float)(sign * s * u[i]) : 0.0f;
     if (t == 0) {
       sv_out[(size_t)p * k + j] = s;
       var_out[(size_t)p * k + j] = lj / (n - 1);

@@ -15,6 +15,17 @@
  * sqrt(lambda), explained variance lambda / (n - 1), ratio lambda / trace(G), components Xc^T u / sqrt(lambda) and scores
  * sqrt(lambda) * u, each component negated so that its entry of largest magnitude (first index on ties) is positive.
  * Every output element is summed in a fixed order: a problem's result does not depend on P or on its neighbours.
+ *
+ * Repeated eigenvalues.  Where lambda repeats (or nearly does), the contract is the subspace and not the basis: the
+ * components of the group are an orthonormal basis of the same span as sklearn's, each with the sign rule applied, and
+ * scores = Xc . components^T holds for them; which basis is returned is fixed (the result is still bit-stable), but it is
+ * not sklearn's.
+ *
+ * Null directions.  The eigen stage resolves lambda no finer than n * DBL_EPSILON * ||T||, T the tridiagonal form of G (the
+ * amount it widens its own Gershgorin interval by).  A top-k lambda_j at or below that (a rank below k) is reported as
+ * null: its singular value, explained variance and ratio are exactly 0, its component and its score column are exactly
+ * 0, and the status stays DT_PCA_OK.  sklearn returns an arbitrary unit vector there; this library returns zeros, as it
+ * does for a whole problem under DT_PCA_ZERO_VARIANCE, so that the sign of a rounding error never decides an output.
  */
 #ifndef DT_HIP_PCA_H
 #define DT_HIP_PCA_H

@@ -6,7 +6,9 @@ import numpy as np
 
 def pca_ref64(X, k):
     """dict(mean, components [k, E], scores [n, k], singular_values, explained_variance, explained_variance_ratio) of
-    the rows X [n, E] (any dtype; computed on the float64 copy)."""
+    the rows X [n, E] (any dtype; computed on the float64 copy), and beyond the first k: spectrum [min(n, E)], every
+    squared singular value (the eigenvalues of the centred Gram matrix, descending), and basis [min(n, E), E], every
+    right singular vector with the sign rule applied."""
     X = np.asarray(X, dtype=np.float64).reshape(len(X), -1)
     n = X.shape[0]
     mean = X.mean(axis=0)
@@ -18,7 +20,7 @@ def pca_ref64(X, k):
     var = S ** 2 / (n - 1)
     total = var.sum()
     return {"mean": mean, "components": Vt[:k], "scores": U[:, :k] * S[:k], "singular_values": S[:k],
-            "explained_variance": var[:k], "explained_variance_ratio": var[:k] / total}
+            "explained_variance": var[:k], "explained_variance_ratio": var[:k] / total, "spectrum": S ** 2, "basis": Vt}
 
 
 def ambiguous_sign(component, tol=1e-6):

@@ -9,6 +9,7 @@ import torch
 
 from distillation_trajectories_amd import engine
 from distillation_trajectories_amd.analysis.dimensionality.pca import TrajectoryPCA, pca_pairs, pca_sweep
+from pca_cases import compare_vectors as _compare
 from pca_ref64 import ambiguous_sign, pca_ref64
 
 DEV = torch.device("cuda:0")
@@ -21,25 +22,6 @@ def _walk(seed, n, P, E, scale=1.0):
     g = torch.Generator().manual_seed(seed)
     steps = torch.randn(n, P, E, generator=g, dtype=torch.float64) * scale
     return (steps.cumsum(0) + 5.0).float()
-
-
-def _compare(got, ref, k, what):
-    """scores / components / mean to 2e-6 of each vector's max-abs; singular values and variances to 1e-9 relative.  A
-    component whose two largest |entries| are within 1e-6 with opposite signs may carry either sign (svd_flip's choice
-    then rests on rounding)."""
-    def close(a, b, tol):
-        a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-        return np.abs(a - b).max() <= tol * max(np.abs(b).max(), 1e-30)
-    assert close(got["mean"], ref["mean"], 2e-6), what
-    for name in ("singular_values", "explained_variance", "explained_variance_ratio"):
-        assert close(got[name], ref[name], 1e-9), (what, name, got[name], ref[name])
-    for j in range(k):
-        c, s = np.asarray(got["components"][j], np.float64), np.asarray(got["scores"][:, j], np.float64)
-        rc, rs = ref["components"][j], ref["scores"][:, j]
-        if ambiguous_sign(rc) and not close(c, rc, 2e-6):
-            c, s = -c, -s
-        assert close(c, rc, 2e-6), (what, j, np.abs(c - rc).max())
-        assert close(s, rs, 2e-6), (what, j, np.abs(s - rs).max())
 
 
 def _problem(r, p):

@@ -1,6 +1,7 @@
 """The device PCA without a GPU: the float64 yardstick against sklearn, the reference's own (randomized) call against the
 yardstick, the exported surface of include/dt_hip_pca.h, the import surface through the reference's module names, and
-argument checks that fail before any device call."""
+argument checks that fail before any device call; the edge cases of tests/pca_cases.py (their stated spectra, the
+preconditions of the comparers) and the comparers themselves, on right and on wrong answers."""
 import os
 import re
 import subprocess
@@ -10,6 +11,7 @@ import pytest
 import torch
 
 from distillation_trajectories_amd import _hip
+import pca_cases as pc
 from pca_ref64 import pca_ref64
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -135,3 +137,140 @@ def test_bad_arguments_raise_before_any_device_call(monkeypatch):
         TrajectoryPCA(4).fit(np.zeros((3, 8), np.float32))
     with pytest.raises(ValueError):
         TrajectoryPCA(2).transform(np.zeros((3, 8), np.float32))
+
+
+# ---------------------------------------------------------------------------------------------- the edge cases
+ALL_CASES = pc.CASES + ("pairs12", "walk12")
+
+
+def _f32(answer):
+    """the answer as the library returns it: mean, components and scores rounded to fp32"""
+    return {f: (v.astype(np.float32) if f in ("mean", "components", "scores") else v) for f, v in answer.items()}
+
+
+def _resign(answer, rows, j):
+    """the sign rule on component j, its score column following"""
+    c = answer["components"][j]
+    if c[np.argmax(np.abs(c))] < 0:
+        answer["components"][j], answer["scores"][:, j] = -c, -answer["scores"][:, j]
+
+
+@pytest.mark.parametrize("name", ALL_CASES)
+def test_case_has_its_stated_spectrum_and_meets_the_preconditions(name):
+    c = pc.case(name)
+    rows, k, ref = c["rows"], c["k"], c["ref"]
+    n, E = rows.shape
+    assert rows.dtype == np.float32 and not rows.flags.writeable and 1 <= k <= min(16, n - 1, E) and E % 4 == 0
+    pc.check_preconditions(ref, k)
+    lam = pc.spectrum(ref)
+    if name in pc.STATED:
+        want = np.array(pc.STATED[name], np.float64)
+        assert np.abs(lam[:len(want)] - want).max() <= 1e-13 * want[0], lam
+    shapes = {"n2": (2, 8, 1), "n2_split": (2, 8, 1), "n3": (3, 8, 2), "n4": (4, 8, 3), "e4": (40, 4, 4), "k1": (20, 16, 1),
+              "offset": (30, 16, 3), "pairs": (6, 16, 3), "stalled": (8, 16, 3), "identity_k4": (12, 12, 4),
+              "identity_k11": (12, 12, 11), "rank1": (12, 16, 3), "three_points": (15, 16, 4), "near": (24, 16, 4),
+              "big": (20, 16, 3), "small": (20, 16, 3), "pairs12": (12, 16, 3), "walk12": (12, 16, 3)}
+    assert (n, E, k) == shapes[name]
+    nulls = {"rank1": [1, 2], "three_points": [2, 3]}
+    assert pc.null_directions(ref, k) == nulls.get(name, [])
+
+
+def test_cases_are_what_their_names_say():
+    X = pc.case("offset")["rows"].astype(np.float64)
+    assert np.array_equal(X.mean(0), X.mean(0).astype(np.float32)) and abs(X.mean() - 1e4) < 1 and (X.std(0) < 0.2).all()
+    for name, m in (("pairs", np.full(16, 7.0)), ("stalled", np.arange(16) % 5 + 2.0)):
+        X = pc.case(name)["rows"].astype(np.float64)
+        assert np.array_equal(X.mean(0), m) and np.array_equal(X, np.round(X))
+    Xc = pc.case("stalled")["rows"].astype(np.float64) - (np.arange(16) % 5 + 2.0)
+    assert not Xc[:2].any() and Xc[2:].any(1).all()                       # two centred rows are exactly zero
+    G = (pc.case("pairs")["rows"].astype(np.float64) - 7) @ (pc.case("pairs")["rows"].astype(np.float64) - 7).T
+    assert not G[np.abs(np.subtract.outer(np.arange(6) // 2, np.arange(6) // 2)) > 0].any()      # block diagonal
+    X = pc.case("three_points")["rows"].astype(np.float64)
+    assert len(np.unique(X, axis=0)) == 3 and np.array_equal(X.mean(0), np.round(X.mean(0))) and np.array_equal(X[:3], X[12:])
+    lam = pc.spectrum(pc.case("near")["ref"])
+    assert np.abs(lam[:6] / lam[0] - np.array(pc.NEAR_LAMBDA)).max() <= 1e-6 and lam[6] <= 1e-12 * lam[0]
+    assert [pc.clusters(lam)[i] for i in range(3)] == [[0, 1, 2], [3], [4]]
+    for name, scale in (("big", 2.0 ** 40), ("small", 2.0 ** -40)):
+        X = pc.case(name)["rows"]
+        assert 1.0 < np.abs(X).max() / scale < 100.0 and np.isfinite(X).all()
+    assert pc.case("n2_split")["split"] == 1
+    assert np.array_equal(pc.case("pairs12")["rows"][:6], pc.case("pairs")["rows"])
+
+
+@pytest.mark.parametrize("name", ALL_CASES)
+def test_comparer_accepts_the_reference_answer(name):
+    """in float64, and rounded to fp32 as the library returns it: the bounds are attainable on every case"""
+    c = pc.case(name)
+    answer = pc.reference_answer(c["ref"], c["k"])
+    fig = pc.compare(answer, c["rows"], c["ref"], c["k"], name)
+    assert max(fig.values()) <= 1e-12, fig
+    pc.compare(_f32(answer), c["rows"], c["ref"], c["k"], name)
+    if name in pc.SEPARATED:
+        pc.compare_vectors(_f32(answer), c["ref"], c["k"], name)
+
+
+@pytest.mark.parametrize("name,members", [("pairs", [0, 1]), ("stalled", [0, 1]), ("identity_k4", list(range(11))),
+                                          ("identity_k11", list(range(11))), ("near", [0, 1, 2])])
+def test_comparer_accepts_a_rotated_basis_of_a_repeated_cluster(name, members):
+    c = pc.case(name)
+    rows, k, ref = c["rows"], c["k"], c["ref"]
+    answer = pc.reference_answer(ref, k)
+    Q = np.linalg.qr(np.random.RandomState(7).standard_normal((len(members), len(members))))[0]
+    mixed = Q @ ref["basis"][members]                                      # another orthonormal basis of the same span
+    centred = rows.astype(np.float64) - ref["mean"]
+    for j in (j for j in members if j < k):
+        answer["components"][j], answer["scores"][:, j] = mixed[j], centred @ mixed[j]
+        _resign(answer, rows, j)
+    assert not pc.close(answer["components"][0], ref["components"][0], 1e-2)
+    pc.compare(_f32(answer), rows, ref, k, name)
+    with pytest.raises(AssertionError):
+        pc.compare_vectors(_f32(answer), ref, k, name)                     # the old comparison is wrong here
+
+
+@pytest.mark.parametrize("name", ["pairs", "identity_k4", "three_points", "near", "walk12"])
+def test_comparer_rejects_wrong_answers(name):
+    c = pc.case(name)
+    rows, k, ref = c["rows"], c["k"], c["ref"]
+    lam = pc.spectrum(ref)
+    right = pc.reference_answer(ref, k)
+    members = pc.clusters(lam)[0]
+    outside = ref["basis"][members[-1] + 1]                                # a unit vector outside component 0's cluster
+
+    def wrong(change):
+        answer = {f: v.copy() for f, v in right.items()}
+        change(answer)
+        return _f32(answer)
+
+    def mix(a):
+        a["components"][0] += 1e-4 * outside
+    with pytest.raises(AssertionError, match="containment"):
+        pc.compare(wrong(mix), rows, ref, k)
+
+    def scale(a):
+        a["components"][0] *= 1 + 1e-5
+        a["scores"][:, 0] *= 1 + 1e-5                                      # consistent with it: only its length is wrong
+    with pytest.raises(AssertionError, match="orthonormality" if len(members) > 1 else "component"):
+        pc.compare(wrong(scale), rows, ref, k)
+
+    def negate(a):
+        a["scores"][:, 0] *= -1
+    with pytest.raises(AssertionError, match="consistency"):
+        pc.compare(wrong(negate), rows, ref, k)
+
+    dead = pc.null_directions(ref, k)
+    if dead:
+        def noise(a):
+            a["components"][dead[0]] = 7e-9 * ref["components"][dead[0]]
+        with pytest.raises(AssertionError, match="null direction"):
+            pc.compare(wrong(noise), rows, ref, k)
+
+        def noisy_scores(a):
+            a["scores"][:, dead[0]] = 1e-12
+        with pytest.raises(AssertionError, match="null direction"):
+            pc.compare(wrong(noisy_scores), rows, ref, k)
+
+        def noisy_variance(a):
+            a["explained_variance"][dead[-1]] = 1e-30
+            a["singular_values"][dead[-1]] = np.sqrt(1e-30 * (len(rows) - 1))
+        with pytest.raises(AssertionError, match="null direction"):
+            pc.compare(wrong(noisy_variance), rows, ref, k)
