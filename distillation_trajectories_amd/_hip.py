@@ -216,6 +216,20 @@ SPECTRAL_SIGNATURES = {
     "dt_spectral_sum": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_void_p]),
 }
 
+# name -> (restype, argtypes) of every symbol include/dt_hip_swd.h declares (sliced Wasserstein distance between state sets)
+_SWD_ROWS = [c_void_p, c_longlong, c_longlong, c_int]
+_SWD_THETA = [c_void_p, c_longlong, c_int, c_int]
+_SWD_SORTED = [c_void_p, c_longlong, c_void_p, c_int]
+_SWD_OUT = [c_void_p] * 5 + [c_void_p, c_size_t, c_void_p]
+SWD_SIGNATURES = {
+    "dt_swd_sorted_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dt_swd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dt_swd_distance_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "dt_swd_sorted": (c_int, _SWD_ROWS + [c_int] + _SWD_THETA + [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dt_swd_distance": (c_int, _SWD_SORTED * 2 + [c_int, c_int, c_int] + _SWD_OUT),
+    "dt_swd": (c_int, _SWD_ROWS * 2 + [c_int] + _SWD_THETA + [c_int] + _SWD_OUT),
+}
+
 
 class TsneParams(ctypes.Structure):
     """dt_tsne_params of include/dt_hip_tsne.h"""
@@ -242,7 +256,7 @@ def load(path=None):
     for name, (res, args) in {**SIGNATURES, **NOISE_SIGNATURES, **INCEPTION_SIGNATURES, **PCA_SIGNATURES,
                               **FID_SIGNATURES, **FID_COV_SIGNATURES, **LPIPS_SIGNATURES, **TSNE_SIGNATURES, **QUALITY_SIGNATURES,
                               **QUALITY_STREAM_SIGNATURES, **EDIT_SIGNATURES, **RNG_SIGNATURES, **ALIGN_SIGNATURES,
-                              **CKA_SIGNATURES, **SPECTRAL_SIGNATURES}.items():
+                              **CKA_SIGNATURES, **SPECTRAL_SIGNATURES, **SWD_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -1,9 +1,10 @@
 """Set-level metrics of teacher and student samples (reference analysis/metrics/): FID (fid_score.py), LPIPS along the
 trajectories (perceptual.py) and KID, precision / recall, density / coverage (sample_quality.py), all on the device;
 and, beyond the reference, the alignment of a teacher's and a student's trajectory in time (alignment.py) the
-layer-wise CKA of what their blocks represent (representation.py) and the spatial-frequency spectra of their states
-(spectral.py)."""
+layer-wise CKA of what their blocks represent (representation.py), the spatial-frequency spectra of their states
+(spectral.py) and the sliced Wasserstein distance between their sets of states (sliced_wasserstein.py)."""
 from .alignment import align_trajectories, alignment_pairs, alignment_sweep
 from .representation import cka_layers, cka_sweep
 from .sample_quality import guidance_quality_sweep, quality_sweep
+from .sliced_wasserstein import sliced_wasserstein_pairs, sliced_wasserstein_sweep, sliced_wasserstein_trajectories
 from .spectral import spectral_pairs, spectral_sweep, spectral_trajectories

@@ -60,6 +60,9 @@ enum KernelClass {   // the convolution classes come first: ConvClass (dt_conv_f
   KC_WASSERSTEIN, KC_RESAMPLE, KC_FUSED, KC_PAIR_METRICS,
   KC_CONVS_PAIR,     // launches that the strip kernel's NH = 2 form serves (dt_conv_strip_pair.h): not a ConvClass, it has no form row
   KC_SPECTRAL,       // the spectra of dt_spectral.hip: table sort, transform and binning, sample sums
+  // the sliced Wasserstein distance of dt_swd.hip: NaN / Inf scan and status, projection, sort of one set, sort of both
+  // with the distance, distance of sorted sets, per-problem mean and maximum
+  KC_SWD_SCAN, KC_SWD_PROJECT, KC_SWD_SORT, KC_SWD_SORT_PAIR, KC_SWD_PAIR, KC_SWD_REDUCE,
   KC_COUNT
 };
 struct ProfileScope {

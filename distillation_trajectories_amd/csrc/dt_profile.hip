@@ -29,7 +29,8 @@ struct Profiler {
 const char *kClassName[KC_COUNT - KC_CONV_COUNT] = {
     "splitk_epilogue_kernel", "first_conv_kernel", "maxpool_kernel", "upcat_kernel", "head_kernel", "head_upsample_kernel",
     "time_bias_kernel", "cfg_update_kernel", "traj_metrics_kernel", "wasserstein_kernel", "resampled_distance_kernel",
-    "unet_fused_kernel", "pair_metrics_kernel", "conv_strip_pair_bf16x6_kernel<256,128>", "spectral_kernel"};
+    "unet_fused_kernel", "pair_metrics_kernel", "conv_strip_pair_bf16x6_kernel<256,128>", "spectral_kernel",
+    "swd_scan_kernel", "swd_project_kernel", "swd_sort_kernel", "swd_pair_kernel<sort>", "swd_pair_kernel", "swd_reduce_kernel"};
 // the printed name of a class: a convolution class is named after the form(s) that carry it (dt_conv_forms.h)
 const char *class_name(int cls) {
   switch (cls) {

@@ -1643,6 +1643,193 @@ def _spectral_call(X, Y, C, H, W, bins, sum_samples, workspace_bytes):
     return res
 
 
+# ---------------------------------------------------------------------- sliced Wasserstein distance (include/dt_hip_swd.h)
+SWD_MAX_N, SWD_MAX_E, SWD_MAX_L, SWD_MAX_P = 2048, 1 << 20, 4096, 1 << 16
+SWD_OK, SWD_NONFINITE = 0, 1
+SWD_SORTED_WORKSPACE_BYTES = 256
+_SWD_DIRECTIONS = {}            # (E, L, seed) -> float32 [L, E] on the host
+_SWD_DEVICE_DIRECTIONS = {}     # (E, L, seed, device) -> the same on a device
+
+
+class SwdSorted(collections.namedtuple("SwdSorted", "sorted status n directions")):
+    """``device_swd_sorted``'s result: sorted [P, L, n] float64 and status [P] int32 on the device, the rows per set ``n``
+    and the device tensor of directions [L, E] the projections were made with."""
+    __slots__ = ()
+
+
+def swd_directions(E, L, seed=0):
+    """L directions in R^E for ``device_swd``: float32 [L, E] on the host.  Drawn as float64 normals from a torch CPU
+    generator of their own seeded with ``seed`` (the global generator is neither read nor advanced), every row divided by
+    its float64 norm and then rounded to float32, so a row's norm is 1 to float32 rounding.  Kept per (E, L, seed): the
+    same tensor comes back, and must not be written to."""
+    E, L, seed = _count(E, "E", 1), _count(L, "L", 1), _count(seed, "seed")
+    if E > SWD_MAX_E or L > SWD_MAX_L:
+        raise ValueError(f"directions take E <= {SWD_MAX_E} and L <= {SWD_MAX_L}, got E={E}, L={L}")
+    key = (E, L, seed)
+    if key not in _SWD_DIRECTIONS:
+        gen = torch.Generator(device="cpu")
+        gen.manual_seed(seed)
+        d = torch.randn(L, E, dtype=torch.float64, generator=gen)
+        _SWD_DIRECTIONS[key] = (d / d.norm(dim=1, keepdim=True)).to(torch.float32)
+    return _SWD_DIRECTIONS[key]
+
+
+def _swd_rows(t, name):
+    """(tensor, P, n, E, problem stride, row stride) of a set of rows per state: [P, n, E] (contiguous or a view) or one
+    set [n, E] (P = 1); read in place when the rows themselves are contiguous, copied otherwise"""
+    t = _f32_rows(t, name, "[states, n, E] or [n, E]")
+    E, n = t.shape[-1], t.shape[-2]
+    P = t.shape[0] if t.dim() == 3 else 1
+    if not (1 <= n <= SWD_MAX_N and 1 <= E <= SWD_MAX_E and 1 <= P <= SWD_MAX_P):
+        raise ValueError(f"{name} must hold 1 .. {SWD_MAX_P} states of 1 .. {SWD_MAX_N} rows of 1 .. {SWD_MAX_E} floats, "
+                         f"got shape {tuple(t.shape)}")
+    if (E > 1 and t.stride(-1) != 1) or any(s < 0 for s in t.stride()):
+        t = t.contiguous()
+    return (t, P, n, E, t.stride(0), t.stride(1)) if t.dim() == 3 else (t, 1, n, E, 0, t.stride(0))
+
+
+def _swd_theta(directions, E=None):
+    """directions as given: a float32 tensor [L, E] with unit column stride, on any device"""
+    if not isinstance(directions, torch.Tensor) or directions.dtype != torch.float32 or directions.dim() != 2:
+        raise ValueError("directions must be a float32 torch tensor [L, E]")
+    L, Ed = directions.shape
+    if not 1 <= L <= SWD_MAX_L or not 1 <= Ed <= SWD_MAX_E:
+        raise ValueError(f"directions must be [L, E] with L <= {SWD_MAX_L} and E <= {SWD_MAX_E}, got {tuple(directions.shape)}")
+    if E is not None and Ed != E:
+        raise ValueError(f"the directions live in R^{Ed}, the rows in R^{E}")
+    if (Ed > 1 and directions.stride(1) != 1) or directions.stride(0) < 0:
+        directions = directions.contiguous()
+    return directions
+
+
+def _swd_sorted_check(s, name):
+    ok = (isinstance(s.sorted, torch.Tensor) and s.sorted.dtype == torch.float64 and s.sorted.dim() == 3 and s.sorted.is_contiguous()
+          and isinstance(s.status, torch.Tensor) and s.status.dtype == torch.int32 and s.status.is_contiguous()
+          and isinstance(s.directions, torch.Tensor) and s.directions.dtype == torch.float32 and s.directions.dim() == 2
+          and not isinstance(s.n, bool) and isinstance(s.n, (int, np.integer)))
+    if ok:
+        P, L, n = s.sorted.shape
+        ok = (n == s.n and 1 <= n <= SWD_MAX_N and 1 <= L <= SWD_MAX_L and 1 <= P <= SWD_MAX_P and tuple(s.status.shape) == (P,)
+              and s.directions.shape[0] == L and s.status.device == s.sorted.device == s.directions.device)
+    if not ok:
+        raise ValueError(f"{name} is not a SwdSorted of device_swd_sorted")
+
+
+def _same_directions(x, y):
+    return x is y or (x.data_ptr() == y.data_ptr() and x.shape == y.shape and x.stride() == y.stride() and x.device == y.device)
+
+
+def _on_device(t, name):
+    if not t.is_cuda:
+        raise ValueError(f"{name} must be on the device, got {t.device}: the MI355X path has no CPU fallback")
+
+
+def device_swd_sorted(X, directions):
+    """Sorted projections of the sets of X onto ``directions`` (dt_swd_sorted): X is float32 on the device, [P, n, E] (one
+    set of n rows per state; views are read in place) or [n, E]; ``directions`` float32 [L, E] (``swd_directions``, or the
+    caller's own; a host tensor is copied to X's device).  Returns ``SwdSorted`` (sorted [P, L, n] float64 ascending along
+    n, status [P] int32: 1 for a NaN or Inf in the state's rows or in the directions, its columns are then NaN).  Hand the
+    result to ``device_swd`` in place of the tensor to compare one set with many others."""
+    x, P, n, E, ps, rs = _swd_rows(X, "X")
+    theta = _swd_theta(directions, E)
+    _on_device(x, "X")
+    dev = x.device
+    if theta.device != dev:
+        theta = theta.to(dev)
+    L = theta.shape[0]
+    with torch.cuda.device(dev):
+        out = SwdSorted(torch.empty(P, L, n, dtype=torch.float64, device=dev), torch.empty(P, dtype=torch.int32, device=dev),
+                        n, theta)
+        ws = torch.empty(SWD_SORTED_WORKSPACE_BYTES, dtype=torch.uint8, device=dev)
+        check(_hip.load().dt_swd_sorted(ptr(x), ps, rs, n, E, ptr(theta), theta.stride(0), L, P, ptr(out.sorted),
+                                        ptr(out.status), ptr(ws), SWD_SORTED_WORKSPACE_BYTES, stream_ptr()), "dt_swd_sorted")
+    return out
+
+
+def device_swd(a, b, directions=None, n_directions=512, p=2, seed=0, per_direction=False, workspace_bytes=None):
+    """Sliced Wasserstein distance between the sets of ``a`` and of ``b``, state by state (dt_swd, or dt_swd_distance when
+    a side comes sorted).  A side is a float32 device tensor [P, n, E] (one set of n rows per state; n may differ between
+    the sides; views are read in place) or [n, E], or the ``SwdSorted`` of ``device_swd_sorted``; a side with one state is
+    shared by all states of the other.  ``directions``: float32 [L, E]; None: those a sorted side was made with, else
+    ``swd_directions(E, n_directions, seed)``.  A sorted side made with other directions is refused.
+    Returns device tensors {mean_w [P] float64 (the mean over the directions of W_p^p), max_w [P] (the largest), argmax [P]
+    int32 (the first direction that reaches it), status [P] int32 (1: a NaN or Inf in the state's rows or the directions;
+    its outputs are NaN, argmax -1)} and, with ``per_direction``, w [P, L].  The p-th root is the caller's (float64).
+    ``workspace_bytes``: a cap on the scratch of dt_swd; the states then take turns, with the same bits.  The contract is
+    in include/dt_hip_swd.h."""
+    if isinstance(p, bool) or not isinstance(p, (int, np.integer)) or p not in (1, 2):
+        raise ValueError(f"p={p!r} must be 1 or 2")
+    cap = None if workspace_bytes is None else _count(workspace_bytes, "workspace_bytes")
+    sides = []
+    for side, name in ((a, "a"), (b, "b")):
+        if isinstance(side, SwdSorted):
+            _swd_sorted_check(side, name)
+            sides.append(None)
+        else:
+            sides.append(_swd_rows(side, name))
+    widths = {s[3] for s in sides if s is not None} | {s.directions.shape[1] for s in (a, b) if isinstance(s, SwdSorted)}
+    if len(widths) != 1:
+        raise ValueError(f"a and b must have rows of one width, got {sorted(widths)}")
+    E = widths.pop()
+    made = [s.directions for s in (a, b) if isinstance(s, SwdSorted)]
+    if directions is not None:
+        theta = _swd_theta(directions, E)
+    elif made:
+        theta = made[0]
+    else:
+        theta = swd_directions(E, _count(n_directions, "n_directions", 1), seed)
+    if any(not _same_directions(m, theta) for m in made):
+        raise ValueError("a sorted side was made with other directions than the ones given")
+    counts = [s.sorted.shape[0] if isinstance(s, SwdSorted) else r[1] for s, r in zip((a, b), sides)]
+    P = max(counts)
+    if any(c not in (1, P) for c in counts):
+        raise ValueError(f"a has {counts[0]} states and b {counts[1]}: equal numbers, or one state on a side")
+    tensors = [s.sorted if isinstance(s, SwdSorted) else r[0] for s, r in zip((a, b), sides)]
+    for t, name in zip(tensors, ("a", "b")):
+        _on_device(t, name)
+    dev = tensors[0].device
+    if tensors[1].device != dev:
+        raise ValueError(f"a is on {dev}, b on {tensors[1].device}")
+    if theta.device != dev:      # (not with a sorted side: its directions are where it is)
+        key = (E, theta.shape[0], seed, str(dev))
+        if directions is None:
+            if key not in _SWD_DEVICE_DIRECTIONS:
+                _SWD_DEVICE_DIRECTIONS[key] = theta.to(dev)
+            theta = _SWD_DEVICE_DIRECTIONS[key]
+        else:
+            theta = theta.to(dev)
+    L = theta.shape[0]
+    lib = _hip.load()
+    n_a, n_b = (s.n if isinstance(s, SwdSorted) else r[2] for s, r in zip((a, b), sides))
+    if not made:
+        least, ws_bytes = lib.dt_swd_workspace_bytes(1, n_a, n_b, L), lib.dt_swd_workspace_bytes(P, n_a, n_b, L)
+        if cap is not None:
+            if cap < least:
+                raise ValueError(f"workspace_bytes={cap} is below the {least} bytes that one state takes")
+            ws_bytes = min(ws_bytes, cap)
+    else:
+        ws_bytes = lib.dt_swd_distance_workspace_bytes(P, L)
+    with torch.cuda.device(dev):
+        res = {"mean_w": torch.empty(P, dtype=torch.float64, device=dev), "max_w": torch.empty(P, dtype=torch.float64, device=dev),
+               "argmax": torch.empty(P, dtype=torch.int32, device=dev), "status": torch.empty(P, dtype=torch.int32, device=dev)}
+        w = torch.empty(P, L, dtype=torch.float64, device=dev) if per_direction else None
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        outs = (ptr(w) if per_direction else None, ptr(res["mean_w"]), ptr(res["max_w"]), ptr(res["argmax"]), ptr(res["status"]),
+                ptr(ws), ws_bytes, stream_ptr())
+        if not made:
+            (xa, Pa, _, _, a_ps, a_rs), (xb, Pb, _, _, b_ps, b_rs) = sides
+            check(lib.dt_swd(ptr(xa), a_ps if Pa == P else 0, a_rs, n_a, ptr(xb), b_ps if Pb == P else 0, b_rs, n_b, E,
+                             ptr(theta), theta.stride(0), L, P, p, *outs), "dt_swd")
+        else:
+            sa, sb = (s if isinstance(s, SwdSorted) else device_swd_sorted(s, theta) for s in (a, b))
+            stride = lambda s: s.sorted.stride(0) if s.sorted.shape[0] == P and P > 1 else 0
+            check(lib.dt_swd_distance(ptr(sa.sorted), stride(sa), ptr(sa.status), n_a, ptr(sb.sorted), stride(sb), ptr(sb.status),
+                                      n_b, L, P, p, *outs), "dt_swd_distance")
+        if per_direction:
+            res["w"] = w
+    return res
+
+
 # ---------------------------------------------------------------------- Fréchet distance (include/dt_hip_fid.h)
 FID_MAX_SIDE = 2048
 FID_MAX_ROWS = 32768
