@@ -230,6 +230,15 @@ SWD_SIGNATURES = {
     "dt_swd": (c_int, _SWD_ROWS * 2 + [c_int] + _SWD_THETA + [c_int] + _SWD_OUT),
 }
 
+# name -> (restype, argtypes) of every symbol include/dt_hip_sinkhorn.h declares (entropic transport cost between state sets)
+_SINKHORN_SETS = _SWD_ROWS * 2 + [c_int, c_int, c_int]            # a, b, E, P, p
+_SINKHORN_WS = [c_void_p, c_size_t, c_void_p]
+SINKHORN_SIGNATURES = {
+    "dt_sinkhorn_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dt_sinkhorn_mean_cost": (c_int, _SINKHORN_SETS + [c_void_p, c_void_p] + _SINKHORN_WS),
+    "dt_sinkhorn_ot": (c_int, _SINKHORN_SETS + [c_void_p, c_int, c_double] + [c_void_p] * 6 + _SINKHORN_WS),
+}
+
 
 class TsneParams(ctypes.Structure):
     """dt_tsne_params of include/dt_hip_tsne.h"""
@@ -256,7 +265,8 @@ def load(path=None):
     for name, (res, args) in {**SIGNATURES, **NOISE_SIGNATURES, **INCEPTION_SIGNATURES, **PCA_SIGNATURES,
                               **FID_SIGNATURES, **FID_COV_SIGNATURES, **LPIPS_SIGNATURES, **TSNE_SIGNATURES, **QUALITY_SIGNATURES,
                               **QUALITY_STREAM_SIGNATURES, **EDIT_SIGNATURES, **RNG_SIGNATURES, **ALIGN_SIGNATURES,
-                              **CKA_SIGNATURES, **SPECTRAL_SIGNATURES, **SWD_SIGNATURES}.items():
+                              **CKA_SIGNATURES, **SPECTRAL_SIGNATURES, **SWD_SIGNATURES,
+                              **SINKHORN_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

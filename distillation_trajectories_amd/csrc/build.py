@@ -12,7 +12,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["dt_conv.hip", "dt_conv_bf16.hip", "dt_conv_strip.hip", "dt_conv_strip_pair.hip", "dt_layers.hip", "dt_update.hip", "dt_metrics.hip", "dt_fused.hip", "dt_profile.hip", "dt_unet.hip",
-           "dt_unet_forward.hip", "dt_unet_tune.hip", "dt_sample.hip", "dt_featnet.hip", "dt_inception.hip", "dt_pca.hip", "dt_fid.hip", "dt_lpips.hip", "dt_tsne.hip", "dt_quality.hip", "dt_quality_stream.hip", "dt_edit.hip", "dt_rng.hip", "dt_align.hip", "dt_cka.hip", "dt_spectral.hip", "dt_swd.hip"]
+           "dt_unet_forward.hip", "dt_unet_tune.hip", "dt_sample.hip", "dt_featnet.hip", "dt_inception.hip", "dt_pca.hip", "dt_fid.hip", "dt_lpips.hip", "dt_tsne.hip", "dt_quality.hip", "dt_quality_stream.hip", "dt_edit.hip", "dt_rng.hip", "dt_align.hip", "dt_cka.hip", "dt_spectral.hip", "dt_swd.hip", "dt_sinkhorn.hip"]
 HEADERS = ["dt_internal.h", "dt_conv_forms.h", "dt_conv_rows.h", "dt_batch.h", "dt_dense64.h", "dt_quality_math.h", "dt_featnet.h", "dt_conv_epilogue.h", "dt_conv_walk.h", "dt_conv_strip_kernel.h", "dt_conv_strip_pair.h", "dt_update_math.h", "dt_fused.h", "dt_unet.h", "dt_unet_layout.h", os.path.join("..", "..", "include", "dt_hip.h"),
            os.path.join("..", "..", "include", "dt_hip_noise.h"),
            os.path.join("..", "..", "include", "dt_hip_inception.h"),
@@ -28,7 +28,8 @@ HEADERS = ["dt_internal.h", "dt_conv_forms.h", "dt_conv_rows.h", "dt_batch.h", "
            os.path.join("..", "..", "include", "dt_hip_align.h"),
            os.path.join("..", "..", "include", "dt_hip_cka.h"),
            os.path.join("..", "..", "include", "dt_hip_spectral.h"),
-           os.path.join("..", "..", "include", "dt_hip_swd.h")]
+           os.path.join("..", "..", "include", "dt_hip_swd.h"),
+           os.path.join("..", "..", "include", "dt_hip_sinkhorn.h")]
 LIB = os.path.join(HERE, "libdt_hip.so")
 ARCH = "gfx950"
 
@@ -110,6 +111,7 @@ ALIGN_SAN_DRIVER = os.path.join(OBJ_DIR, "dt_host_sanitize_align")
 CKA_SAN_DRIVER = os.path.join(OBJ_DIR, "dt_host_sanitize_cka")
 SPECTRAL_SAN_DRIVER = os.path.join(OBJ_DIR, "dt_host_sanitize_spectral")
 SWD_SAN_DRIVER = os.path.join(OBJ_DIR, "dt_host_sanitize_swd")
+SINKHORN_SAN_DRIVER = os.path.join(OBJ_DIR, "dt_host_sanitize_sinkhorn")
 
 
 def build_sanitizer_driver(verbose=False, driver="driver.cpp", out=SAN_DRIVER, sources=None):
@@ -196,6 +198,14 @@ def build_swd_sanitizer_driver(verbose=False):
     return build_sanitizer_driver(verbose, driver="swd_driver.cpp", out=SWD_SAN_DRIVER, sources=["dt_swd.hip", "dt_profile.hip"])
 
 
+def build_sinkhorn_sanitizer_driver(verbose=False):
+    """tests/host_sanitize/sinkhorn_driver.cpp with csrc/dt_sinkhorn.hip (and csrc/dt_profile.hip, whose ProfileScope it opens),
+    host code instrumented in the same way: the size query and argument errors of include/dt_hip_sinkhorn.h, none of which
+    reaches the GPU: csrc/_build/dt_host_sanitize_sinkhorn (run by tests/test_sinkhorn_host.py, without a GPU)."""
+    return build_sanitizer_driver(verbose, driver="sinkhorn_driver.cpp", out=SINKHORN_SAN_DRIVER,
+                                  sources=["dt_sinkhorn.hip", "dt_profile.hip"])
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     if "--sanitize" in sys.argv:
@@ -209,3 +219,4 @@ if __name__ == "__main__":
         print(build_cka_sanitizer_driver(verbose=True))
         print(build_spectral_sanitizer_driver(verbose=True))
         print(build_swd_sanitizer_driver(verbose=True))
+        print(build_sinkhorn_sanitizer_driver(verbose=True))

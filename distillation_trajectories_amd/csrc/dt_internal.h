@@ -63,6 +63,10 @@ enum KernelClass {   // the convolution classes come first: ConvClass (dt_conv_f
   // the sliced Wasserstein distance of dt_swd.hip: NaN / Inf scan and status, projection, sort of one set, sort of both
   // with the distance, distance of sorted sets, per-problem mean and maximum
   KC_SWD_SCAN, KC_SWD_PROJECT, KC_SWD_SORT, KC_SWD_SORT_PAIR, KC_SWD_PAIR, KC_SWD_REDUCE,
+  // the entropic transport cost of dt_sinkhorn.hip, a class per kernel: NaN / Inf scan, state words and g = 0, cost matrix,
+  // row half-step, column half-step, per-problem finish, row sums and mean of dt_sinkhorn_mean_cost
+  KC_SINKHORN_SCAN, KC_SINKHORN_INIT, KC_SINKHORN_COST, KC_SINKHORN_ROW, KC_SINKHORN_COL, KC_SINKHORN_FINISH,
+  KC_SINKHORN_ROWSUM, KC_SINKHORN_MEAN,
   KC_COUNT
 };
 struct ProfileScope {

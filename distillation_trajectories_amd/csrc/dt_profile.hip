@@ -30,7 +30,9 @@ const char *kClassName[KC_COUNT - KC_CONV_COUNT] = {
     "splitk_epilogue_kernel", "first_conv_kernel", "maxpool_kernel", "upcat_kernel", "head_kernel", "head_upsample_kernel",
     "time_bias_kernel", "cfg_update_kernel", "traj_metrics_kernel", "wasserstein_kernel", "resampled_distance_kernel",
     "unet_fused_kernel", "pair_metrics_kernel", "conv_strip_pair_bf16x6_kernel<256,128>", "spectral_kernel",
-    "swd_scan_kernel", "swd_project_kernel", "swd_sort_kernel", "swd_pair_kernel<sort>", "swd_pair_kernel", "swd_reduce_kernel"};
+    "swd_scan_kernel", "swd_project_kernel", "swd_sort_kernel", "swd_pair_kernel<sort>", "swd_pair_kernel", "swd_reduce_kernel",
+    "sinkhorn_scan_kernel", "sinkhorn_init_kernel", "sinkhorn_cost_kernel", "sinkhorn_row_kernel", "sinkhorn_col_kernel",
+    "sinkhorn_finish_kernel", "sinkhorn_rowsum_kernel", "sinkhorn_mean_kernel"};
 // the printed name of a class: a convolution class is named after the form(s) that carry it (dt_conv_forms.h)
 const char *class_name(int cls) {
   switch (cls) {

@@ -1830,6 +1830,187 @@ def device_swd(a, b, directions=None, n_directions=512, p=2, seed=0, per_directi
     return res
 
 
+# ---------------------------------------------------------------------- entropic transport cost (include/dt_hip_sinkhorn.h)
+SINKHORN_MAX_N, SINKHORN_MAX_E, SINKHORN_MAX_P, SINKHORN_MAX_ITER = 2048, 1 << 20, 1 << 16, 10000
+SINKHORN_OK, SINKHORN_NONFINITE, SINKHORN_BAD_EPS, SINKHORN_NOT_CONVERGED = 0, 1, 2, 4
+SINKHORN_DEFAULT_MAX_ITER, SINKHORN_DEFAULT_TOL = 300, 1e-6
+
+
+def _sinkhorn_p(p):
+    if isinstance(p, bool) or not isinstance(p, (int, np.integer)) or p not in (1, 2):
+        raise ValueError(f"p={p!r} must be 1 or 2")
+    return int(p)
+
+
+def _sinkhorn_sides(a, b):
+    """the two row sets of a Sinkhorn call ((tensor, P, n, E, problem stride, row stride) each, as ``_swd_rows`` gives them;
+    a side with one state has problem stride 0) and the number of problems; every error a ValueError, the device last"""
+    sides = [_swd_rows(a, "a"), _swd_rows(b, "b")]
+    if sides[0][3] != sides[1][3]:
+        raise ValueError(f"a and b must have rows of one width, got {sides[0][3]} and {sides[1][3]}")
+    P = max(sides[0][1], sides[1][1])
+    if any(s[1] not in (1, P) for s in sides):
+        raise ValueError(f"a has {sides[0][1]} states and b {sides[1][1]}: equal numbers, or one state on a side")
+    return [(t, Ps, n, E, ps if Ps == P and P > 1 else 0, rs) for t, Ps, n, E, ps, rs in sides], P
+
+
+def _sinkhorn_devices(sides):
+    for (t, *_), name in zip(sides, ("a", "b")):
+        _on_device(t, name)
+    if sides[0][0].device != sides[1][0].device:
+        raise ValueError(f"a is on {sides[0][0].device}, b on {sides[1][0].device}")
+    return sides[0][0].device
+
+
+def _sinkhorn_workspace(lib, P, n_a, n_b, cap):
+    least, ws_bytes = lib.dt_sinkhorn_workspace_bytes(1, n_a, n_b), lib.dt_sinkhorn_workspace_bytes(P, n_a, n_b)
+    if cap is not None:
+        if cap < least:
+            raise ValueError(f"workspace_bytes={cap} is below the {least} bytes that one state takes")
+        ws_bytes = min(ws_bytes, cap)
+    return ws_bytes
+
+
+def device_sinkhorn_mean_cost(a, b, p=2, workspace_bytes=None):
+    """Mean over all pairs (i, j) of the cost C_ij = |a_i - b_j|^p between the sets of ``a`` and of ``b``, state by state
+    (dt_sinkhorn_mean_cost): float32 device tensors [P, n, E] or [n, E] as ``device_swd`` takes them (views are read in
+    place; a side with one state is shared by all states of the other).  Returns {mean_cost [P] float64, status [P] int32
+    (1: a NaN or Inf in the state's rows, its mean is NaN)} on the device: what an epsilon is made from without a host
+    round trip."""
+    p = _sinkhorn_p(p)
+    cap = None if workspace_bytes is None else _count(workspace_bytes, "workspace_bytes")
+    sides, P = _sinkhorn_sides(a, b)
+    dev = _sinkhorn_devices(sides)
+    (xa, _, n_a, E, a_ps, a_rs), (xb, _, n_b, _, b_ps, b_rs) = sides
+    lib = _hip.load()
+    ws_bytes = _sinkhorn_workspace(lib, P, n_a, n_b, cap)
+    with torch.cuda.device(dev):
+        res = {"mean_cost": torch.empty(P, dtype=torch.float64, device=dev), "status": torch.empty(P, dtype=torch.int32, device=dev)}
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        check(lib.dt_sinkhorn_mean_cost(ptr(xa), a_ps, a_rs, n_a, ptr(xb), b_ps, b_rs, n_b, E, P, p, ptr(res["mean_cost"]),
+                                        ptr(res["status"]), ptr(ws), ws_bytes, stream_ptr()), "dt_sinkhorn_mean_cost")
+    return res
+
+
+def _sinkhorn_epsilon(epsilon, P):
+    """epsilon as given: a positive finite float (every state), or a float64 tensor [P] (checked on the device, per state)"""
+    if isinstance(epsilon, torch.Tensor):
+        if epsilon.dtype != torch.float64 or tuple(epsilon.shape) != (P,):
+            raise ValueError(f"epsilon must be a float or a float64 tensor [{P}], got {epsilon.dtype} {tuple(epsilon.shape)}")
+        return epsilon
+    if isinstance(epsilon, bool) or not isinstance(epsilon, (int, float, np.integer, np.floating)):
+        raise ValueError(f"epsilon={epsilon!r} must be a float or a float64 device tensor")
+    if not (np.isfinite(epsilon) and epsilon > 0):
+        raise ValueError(f"epsilon={epsilon!r} must be positive and finite")
+    return float(epsilon)
+
+
+def _sinkhorn_stop(max_iter, tol):
+    max_iter = _count(max_iter, "max_iter", 1)
+    if max_iter > SINKHORN_MAX_ITER:
+        raise ValueError(f"max_iter={max_iter} is above {SINKHORN_MAX_ITER}")
+    if isinstance(tol, bool) or not isinstance(tol, (int, float, np.integer, np.floating)) or not (np.isfinite(tol) and tol >= 0):
+        raise ValueError(f"tol={tol!r} must be a finite float >= 0")
+    return max_iter, float(tol)
+
+
+def device_sinkhorn_ot(a, b, epsilon, p=2, max_iter=SINKHORN_DEFAULT_MAX_ITER, tol=SINKHORN_DEFAULT_TOL, potentials=False,
+                       workspace_bytes=None):
+    """Entropic optimal-transport cost OT_eps between the sets of ``a`` and of ``b`` with uniform weights, state by state
+    (dt_sinkhorn_ot): float32 device tensors [P, n, E] or [n, E] as ``device_swd`` takes them (n may differ between the
+    sides; views are read in place; a side with one state is shared by all states of the other).  ``epsilon``: a float, or a
+    float64 device tensor [P] (one per state, never brought to the host).  Sinkhorn steps on the dual potentials in the log
+    domain with cost |a_i - b_j|^p; a state stops at the first step whose marginal error is <= ``tol`` (tol = 0: exactly
+    ``max_iter`` steps).
+    Returns device tensors {ot [P] float64, err [P] float64 (the marginal error of the last step run), iters [P] int32,
+    status [P] int32 (bits: 1 a NaN or Inf in the state's rows, 2 an epsilon that is not finite or <= 0 -- ot and err are
+    then NaN, iters 0 --, 4 not converged within max_iter: the values are still given)} and, with ``potentials``, f [P, n_a]
+    and g [P, n_b].  ``workspace_bytes``: a cap on the scratch; the states then take turns, with the same bits.  There is
+    no CPU fallback.  The contract is in include/dt_hip_sinkhorn.h."""
+    p = _sinkhorn_p(p)
+    max_iter, tol = _sinkhorn_stop(max_iter, tol)
+    cap = None if workspace_bytes is None else _count(workspace_bytes, "workspace_bytes")
+    sides, P = _sinkhorn_sides(a, b)
+    epsilon = _sinkhorn_epsilon(epsilon, P)
+    dev = _sinkhorn_devices(sides)
+    if isinstance(epsilon, torch.Tensor):
+        _on_device(epsilon, "epsilon")
+        if epsilon.device != dev:
+            raise ValueError(f"epsilon is on {epsilon.device}, the rows on {dev}")
+        epsilon = epsilon.contiguous()
+    (xa, _, n_a, E, a_ps, a_rs), (xb, _, n_b, _, b_ps, b_rs) = sides
+    lib = _hip.load()
+    ws_bytes = _sinkhorn_workspace(lib, P, n_a, n_b, cap)
+    with torch.cuda.device(dev):
+        eps = epsilon if isinstance(epsilon, torch.Tensor) else torch.full((P,), epsilon, dtype=torch.float64, device=dev)
+        res = {"ot": torch.empty(P, dtype=torch.float64, device=dev), "err": torch.empty(P, dtype=torch.float64, device=dev),
+               "iters": torch.empty(P, dtype=torch.int32, device=dev), "status": torch.empty(P, dtype=torch.int32, device=dev)}
+        if potentials:
+            res["f"] = torch.empty(P, n_a, dtype=torch.float64, device=dev)
+            res["g"] = torch.empty(P, n_b, dtype=torch.float64, device=dev)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        check(lib.dt_sinkhorn_ot(ptr(xa), a_ps, a_rs, n_a, ptr(xb), b_ps, b_rs, n_b, E, P, p, ptr(eps), max_iter, tol,
+                                 ptr(res["ot"]), ptr(res["err"]), ptr(res["iters"]), ptr(res["status"]),
+                                 ptr(res["f"]) if potentials else None, ptr(res["g"]) if potentials else None, ptr(ws), ws_bytes,
+                                 stream_ptr()), "dt_sinkhorn_ot")
+    return res
+
+
+def _sinkhorn_self(term, name, P, dev=None):
+    """a self term handed in: the ``ot`` tensor (or the whole result) of an earlier ``device_sinkhorn_ot(x, x, ..)``"""
+    ot = term["ot"] if isinstance(term, dict) and "ot" in term else term
+    if not isinstance(ot, torch.Tensor) or ot.dtype != torch.float64 or ot.dim() != 1 or ot.shape[0] not in (1, P):
+        raise ValueError(f"{name} must be the float64 ot tensor [{P}] (or [1]) of a self term")
+    if dev is not None and ot.device != dev:
+        raise ValueError(f"{name} is on {ot.device}, the rows on {dev}")
+    return term if isinstance(term, dict) else {"ot": ot}
+
+
+def device_sinkhorn_divergence(a, b, epsilon, p=2, max_iter=SINKHORN_DEFAULT_MAX_ITER, tol=SINKHORN_DEFAULT_TOL,
+                               workspace_bytes=None, self_a=None, self_b=None):
+    """Debiased Sinkhorn divergence S_eps(a, b) = OT_eps(a, b) - (0.5 OT_eps(a, a) + 0.5 OT_eps(b, b)), state by state:
+    three ``device_sinkhorn_ot`` calls with one epsilon and that one float64 expression on the device.  All three terms go
+    through the same kernels, so a ``b`` that is a bitwise copy of ``a`` gives exactly 0.0.  ``self_a`` / ``self_b``: a self term already made with the same
+    epsilon, p, max_iter and tol: the whole result of its ``device_sinkhorn_ot`` call, whose err, iters and status then enter
+    the ones returned here, or its bare ``ot`` tensor [P] (or [1] for a shared side), which CARRIES NO STATUS: err, iters
+    and status then cover only the terms run in this call, and a NOT_CONVERGED bit of that self term is the caller's to
+    keep.  A shape that does not fit is refused.  Returns device tensors {divergence, ot_ab, ot_aa,
+    ot_bb [P] float64, err [P] (the largest of the three terms, but for one handed in as a bare tensor), iters [P] (likewise),
+    status [P] (their bits OR-ed)}."""
+    sides, P = _sinkhorn_sides(a, b)
+    kw = dict(p=p, max_iter=max_iter, tol=tol, workspace_bytes=workspace_bytes)
+    _sinkhorn_p(p), _sinkhorn_stop(max_iter, tol), _sinkhorn_epsilon(epsilon, P)
+    if self_a is not None:
+        self_a = _sinkhorn_self(self_a, "self_a", P)
+    if self_b is not None:
+        self_b = _sinkhorn_self(self_b, "self_b", P)
+    dev = _sinkhorn_devices(sides)
+    for term, name in ((self_a, "self_a"), (self_b, "self_b")):
+        if term is not None:
+            _sinkhorn_self(term, name, P, dev)
+
+    def own(side, x):
+        """the self term of a side; a shared side has one state, whose epsilon is the first (a float: the only one)"""
+        if side[1] == 1 and P > 1 and isinstance(epsilon, torch.Tensor):
+            raise ValueError("a side shared by several states needs one epsilon: hand its self term in (self_a / self_b)")
+        return device_sinkhorn_ot(x, x, epsilon, **kw)
+
+    raw = [_swd_rows(a, "a"), _swd_rows(b, "b")]
+    ab = device_sinkhorn_ot(a, b, epsilon, **kw)
+    aa = self_a if self_a is not None else own(raw[0], a)
+    bb = self_b if self_b is not None else own(raw[1], b)
+    ran = [t for t in (ab, aa, bb) if "status" in t]
+    res = {"ot_ab": ab["ot"], "ot_aa": aa["ot"].expand(P), "ot_bb": bb["ot"].expand(P)}
+    res["divergence"] = res["ot_ab"] - (0.5 * res["ot_aa"] + 0.5 * res["ot_bb"])
+    res["err"] = torch.stack([t["err"].expand(P) for t in ran]).amax(dim=0)
+    res["iters"] = torch.stack([t["iters"].expand(P) for t in ran]).amax(dim=0)
+    status = ran[0]["status"].expand(P).clone()
+    for t in ran[1:]:
+        status |= t["status"].expand(P)
+    res["status"] = status
+    return res
+
+
 # ---------------------------------------------------------------------- Fréchet distance (include/dt_hip_fid.h)
 FID_MAX_SIDE = 2048
 FID_MAX_ROWS = 32768
